@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """Benchmark: rasterizer forward+backward on BASELINE.json config 3 (1M Gaussians, 1920x1080, SH deg 3).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times K steps and prints one JSON line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR then writes what the last timed step returned (image, inverse depth, radii and the
+per-Gaussian gradients) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared array by array.
+--full adds every other measurement (the extra fields below), each in passes of its own.
 
 One step on every rank = one forward + backward of the HIP rasterizer (C ABI, include/gsrast.h) for that
 rank's view of the shared 1M-Gaussian scene (view k = the treehill view rotated 2*pi*k/8 about world y),
@@ -13,14 +18,15 @@ of the per-Gaussian parameter gradients plus one all-gather of the compact SH fa
 4: one view per GPU).  The statistics are reduced over ranks only when the model densifies.  Per-GPU work is
 fixed, so scaling is weak.  value = N * Gaussians * W * H / step time (Gaussians*pixels/s, whole job).
 
-Extra fields on the one JSON line:
+Extra fields on the one JSON line with --full:
   roofline      dominant kernel (a composite pass, fp32-VALU-bound): algorithmic flops / its average duration
                 from a hipEvent pair recorded around that kernel's stage on the launch stream on every 4th timed
                 step (the only events in the timed region; SURVEY.md §8(d) flops), with the same launch's
                 algorithmic-bytes HBM figure and PMC traffic beside it;
   cpu_baseline  the oracle (oracle/gsr_oracle.c, C + OpenMP) on the same workload on the host cores;
   stages_ms     average device time of every pipeline stage per step, from a separate untimed pass of K steps
-                with an event pair around every stage.
+                with an event pair around every stage;
+  step_events_ms, train_step   per-step distribution and the full training step, each a pass of its own.
 """
 from __future__ import annotations
 
@@ -44,6 +50,13 @@ TRANS_EXTRA_NS = 2.2   # v_exp / v_rcp cost ~3.5 ns on the same pipe
 EVENT_EVERY = 4  # timed steps per step that carries the dominant kernel's event pair
 SETTLE_S = 0.2   # untimed steps (seconds) right before the timed ones, clocks at steady state
 PY_REFERENCE_CFG3_S = 730.0  # reference Python rasterizer, cfg 3 fwd+bwd, 8-core Xeon
+# --dump-outputs: every array whole up to these row counts, else a fixed seeded sample of its rows.  At cfg 3 the
+# two images are whole (4 floats x 2.07M pixels, 33 MB) and the seven per-Gaussian arrays (63 floats a row) are
+# sampled (16.5 MB); at most 4 x 4 B x DUMP_PIXELS + 63 x 4 B x DUMP_GAUSSIANS = 50 MB at any size.
+DUMP_PIXELS = 1 << 21
+DUMP_GAUSSIANS = 1 << 16
+DUMP_SEED = 0
+DUMP_MAX_BYTES = 64_000_000
 
 CONFIGS = {
     "cfg3": dict(n=1_000_000, W=1920, H=1080, deg=3, stress=0.0,
@@ -58,12 +71,52 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
-def parse():
+def sample_rows(t, axis: int, limit: int):
+    """`t` whole if it has at most `limit` entries along `axis`, else the same sorted sample of `limit` of them on
+    every run (torch.randperm seeded with DUMP_SEED)."""
+    import torch
+    n = t.shape[axis]
+    if n <= limit:
+        return t
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(DUMP_SEED))[:limit].sort().values
+    return t.index_select(axis, idx.to(t.device))
+
+
+def dump_outputs(dirname: str, images: dict, per_gaussian: dict) -> dict:
+    """Write DIR/<name>.npy (float32).  images: (C, H, W) tensors, sampled over pixels as (C, DUMP_PIXELS) when
+    larger; per_gaussian: tensors with one row per Gaussian, sampled over rows beyond DUMP_GAUSSIANS.  Entries that
+    are None are left out.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for name, t in images.items():
+        if t is not None:
+            flat = sample_rows(t.detach().reshape(t.shape[0], -1), 1, DUMP_PIXELS)
+            arrays[name] = flat.reshape(t.shape) if flat.shape[1] == t.shape[1] * t.shape[2] else flat
+    for name, t in per_gaussian.items():
+        if t is not None:
+            arrays[name] = sample_rows(t.detach(), 0, DUMP_GAUSSIANS)
+    arrays = {k: v.to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32; a fixed "
+                         "seeded sample of the larger arrays)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure, in passes of their own, the per-stage times, the dominant kernel's roofline, "
+                         "the per-step distribution, the training step and the CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stage-events", action="store_true", help="time without per-stage hipEvents")
     ap.add_argument("--cpu-budget-s", type=float, default=20.0)
@@ -91,7 +144,7 @@ def parse():
     ap.add_argument("--force-dist", action="store_true",
                     help="take the N>1 path (process group, RCCL exchange) even with one rank, e.g. under "
                          "torchrun --nproc-per-node 1")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 def main():
@@ -166,21 +219,21 @@ def main():
             backward_chunked(st, settings, dcolor, dinv, red.chunk_outputs(), on_chunk=red.start_chunk,
                              compact_sh=red.compact, accumulate_stats=True)
             red.finish(sc.means3D)
-        return st
+        return color, invd, st
 
     # ---- warmup ----
     for _ in range(args.warmup):
-        st = step()
+        color, invd, st = step()
     torch.cuda.synchronize()
 
-    # ---- per-stage breakdown (untimed): an event pair around every stage ----
-    use_events = not args.no_stage_events
+    # ---- per-stage breakdown (--full; untimed): an event pair around every stage ----
+    use_events = args.full and not args.no_stage_events
     stage_avg = {}
     if use_events:
         _native.reset_stage_times()
         _native.set_profiling(True)
         for _ in range(args.steps):
-            st = step()
+            color, invd, st = step()
         torch.cuda.synchronize()
         _native.set_profiling(False)
         stage_avg = {k: (v[0] / v[1] if v[1] else 0.0) for k, v in _native.stage_times().items()}
@@ -208,7 +261,7 @@ def main():
         if more.item() == 0.0:
             break
         for _ in range(10):
-            st = step()
+            color, invd, st = step()
         torch.cuda.synchronize()
     if use_events:
         _native.set_tuning("prof_mask", _native.stage_mask(dom))
@@ -219,7 +272,7 @@ def main():
     for i in range(args.steps):
         if use_events:
             _native.set_profiling(i % EVENT_EVERY == 0)
-        st = step()
+        color, invd, st = step()
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -234,27 +287,40 @@ def main():
         elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / args.steps
 
-    # ---- per-step distribution (separate pass, not the headline): one hipEvent at every step boundary on the
-    # launch stream, SURVEY.md §8(d)'s "median of >= 20 hipEvent-timed steps".  Each event is a stream marker the
-    # next kernel waits behind (~6 us), so these per-step times run slightly above the wall-clock mean. ----
-    n_ev = max(args.steps, 20)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev + 1)]
-    gc.disable()
-    if distributed:
-        dist.barrier()
-    torch.cuda.synchronize()
-    evs[0].record()
-    for i in range(n_ev):
-        st = step()
-        evs[i + 1].record()
-    torch.cuda.synchronize()
-    gc.enable()
-    per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_ev))
-    step_events = {"steps": n_ev, "p50_ms": round(per_step[n_ev // 2], 4),
-                   "p90_ms": round(per_step[min(n_ev - 1, (9 * n_ev) // 10)], 4),
-                   "min_ms": round(per_step[0], 4), "mean_ms": round(sum(per_step) / n_ev, 4)}
+    # ---- --dump-outputs: what the last timed step handed its caller (rank 0's view; gradients after the exchange).
+    # The densification statistics are left out: they are running sums over every step since the start. ----
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        gr = red.grads
+        dumped = dump_outputs(args.dump_outputs, {"color": color, "invdepth": invd},
+                              {"radii": st.radii, "dL_dmeans2D": red.means2D, "dL_dmeans3D": gr["means3D"],
+                               "dL_dscales": gr["scales"], "dL_drotations": gr["rotations"],
+                               "dL_dopacities": gr["opacities"], "dL_dshs": gr["shs"]})
+    del color, invd
 
-    # ---- training step (separate pass, extra field, not the headline): forward + backward + exchange + Adam ----
+    # ---- per-step distribution (--full; separate pass, not the headline): one hipEvent at every step boundary on
+    # the launch stream, SURVEY.md §8(d)'s "median of >= 20 hipEvent-timed steps".  Each event is a stream marker the
+    # next kernel waits behind (~6 us), so these per-step times run slightly above the wall-clock mean. ----
+    step_events = None
+    if args.full:
+        n_ev = max(args.steps, 20)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev + 1)]
+        gc.disable()
+        if distributed:
+            dist.barrier()
+        torch.cuda.synchronize()
+        evs[0].record()
+        for i in range(n_ev):
+            _, _, st = step()
+            evs[i + 1].record()
+        torch.cuda.synchronize()
+        gc.enable()
+        per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_ev))
+        step_events = {"steps": n_ev, "p50_ms": round(per_step[n_ev // 2], 4),
+                       "p90_ms": round(per_step[min(n_ev - 1, (9 * n_ev) // 10)], 4),
+                       "min_ms": round(per_step[0], 4), "mean_ms": round(sum(per_step) / n_ev, 4)}
+
+    # ---- training step (--full; separate pass, extra field, not the headline): forward + backward + exchange + Adam
     # The reference steps torch.optim.Adam(eps=1e-15) over its six per-Gaussian groups right after the backward
     # (gs_lightning_module.py:114-134,168-170).  As there, the optimizer steps the RAW parameters (xyz, features_dc,
     # features_rest and the pre-activation _opacity / _scaling / _rotation of gaussian_model.py) and the rasterizer
@@ -262,7 +328,7 @@ def main():
     # with the learning rates of configs/train_gs.yaml; the SH groups take their gradient in factored form through
     # the fused SH Adam (compact exchange, GaussianAdam.step(sh_views=...)), so no (P, 16, 3) gradient is written.
     train = None
-    if not args.no_train_step:
+    if args.full and not args.no_train_step:
         from gaussian_splatting_lightning_amd.optim import GaussianAdam
         from gaussian_splatting_lightning_amd.activations import activate, activate_backward
         from gaussian_splatting_lightning_amd.multiview import plan_exchange
@@ -376,7 +442,7 @@ def main():
     tot, calls = timed_stages.get(dom, (0.0, 0))
     dom_ms = tot / calls if calls else 0.0  # measured over the timed steps
     roofline = None
-    if dom_ms > 0:
+    if args.full and dom_ms > 0:
         ach = algo_bytes[dom] / (dom_ms * 1e-3) / 1e9
         traffic = None
         pmc_path = os.path.join(REPO, "profiles", "pmc_traffic.json")
@@ -422,9 +488,9 @@ def main():
                             "sum(n_contrib) (SURVEY §8(d)); traffic = PMC HBM bytes per launch "
                             "(profiles/pmc_traffic.json)"}
 
-    # ---- CPU baseline: the oracle on the same workload, rank 0 at N=1 only ----
+    # ---- CPU baseline (--full): the oracle on the same workload, rank 0 at N=1 only ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O
         inp = [t.numpy() for t in (scene.means3D, scene.opacities, scene.scales, scene.rotations, scene.shs)]
         vm, pm_, cp = cam.viewmatrix.numpy(), cam.projmatrix.numpy(), cam.campos.numpy()
@@ -460,15 +526,16 @@ def main():
                    "stage_events": (f"timed steps: dominant kernel only, every {EVENT_EVERY}th step; stages_ms: "
                                     "separate untimed pass"
                                     if use_events else "none")},
+        "full": args.full,
+        **({"dumped_outputs": dumped} if dumped is not None else {}),
         **({"distributed": {"backend": dist.get_backend(), "world_size": world, "exchange": red.describe(),
                             "plan": red.plan,
                             "note": "process group initialised: every step ran the exchange's collectives"}}
            if distributed else {}),
         # also the contributing (pixel, Gaussian) pairs per second (this rank's sum(n_contrib) x N)
         "contrib_pairs_per_s": world * sum_contrib / (ms_per_step * 1e-3),
-        "step_events_ms": step_events,
-        "roofline": roofline, "cpu_baseline": cpu, "train_step": train,
-        "stages_ms": {k: round(v, 4) for k, v in stage_avg.items() if v > 0},
+        **({"step_events_ms": step_events, "roofline": roofline, "cpu_baseline": cpu, "train_step": train,
+            "stages_ms": {k: round(v, 4) for k, v in stage_avg.items() if v > 0}} if args.full else {}),
     }
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -8,12 +8,12 @@
 #   tests[:EXPR]              pytest -m gpu (optionally -k EXPR, "+" for " or "); writes parity.json
 #   rccl                      tests/test_rccl.py (one-rank RCCL group)
 #   smoke                     __graft_entry__.smoke()
-#   bench[:CFG[:ARGS]]        bench.py --config CFG (ARGS: extra flags, ',' for spaces)
-#   forcedist[:CFG[:ARGS]]    torchrun --nproc-per-node 1 bench.py --force-dist (the N > 1 path on one rank)
+#   bench[:CFG[:ARGS]]        bench.py --full --config CFG (ARGS: extra flags, ',' for spaces)
+#   forcedist[:CFG[:ARGS]]    torchrun --nproc-per-node 1 bench.py --full --force-dist (the N > 1 path on one rank)
 #   distov[:CFG]              tools/dist_overhead.py, and the same under rocprofv3 --kernel-trace --stats
 #   ab:CFG:KNOBS[:ROUNDS]     tools/stage_ab.py interleaved knob A/B (KNOBS: name=v1,v2[+name=...])
 #   libab:CFG:LIBA:LIBB       tools/lib_ab.sh interleaved library A/B
-#   kstats[:CFG]              rocprofv3 --kernel-trace --stats over bench.py --config CFG
+#   kstats[:CFG]              rocprofv3 --kernel-trace --stats over bench.py --full --config CFG
 #   pmc:CFG:NAME:COUNTERS     one rocprofv3 --pmc pass over tools/run_steps.py (COUNTERS: ',' for spaces)
 #   round[:CFGS]              tools/gpu_round_profile.sh TAG (PMC passes, bench lines, kernel stats; CFGS ',')
 #   py:SCRIPT[:ARGS]          python SCRIPT ARGS (ARGS: ',' for spaces), 300 s limit
@@ -54,12 +54,12 @@ for step in "$@"; do
       run 200 smoke python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 ;;
     bench)
       cfg=${a1:-cfg3}; extra=${a2:-}
-      run 400 "bench $cfg" python bench.py --config "$cfg" ${extra//,/ } > "$O/bench_${cfg}_$n.json" 2> "$O/bench_${cfg}_$n.err"
+      run 400 "bench $cfg" python bench.py --full --config "$cfg" ${extra//,/ } > "$O/bench_${cfg}_$n.json" 2> "$O/bench_${cfg}_$n.err"
       cat "$O/bench_${cfg}_$n.json" | cut -c1-400 ;;
     forcedist)
       cfg=${a1:-cfg3}; extra=${a2:-}
       run 400 "forcedist $cfg" python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-        --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --config "$cfg" --gpus 1 --force-dist \
+        --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --full --config "$cfg" --gpus 1 --force-dist \
         --no-cpu-baseline ${extra//,/ } > "$O/forcedist_${cfg}_$n.json" 2> "$O/forcedist_${cfg}_$n.err"
       cat "$O/forcedist_${cfg}_$n.json" | cut -c1-400 ;;
     distov)
@@ -82,7 +82,7 @@ for step in "$@"; do
     kstats)
       cfg=${a1:-cfg3}
       run 300 "kstats $cfg" rocprofv3 --kernel-trace --stats -d "$O/kstats_${cfg}_$n" -o run --output-format csv -- \
-        python bench.py --config "$cfg" --no-cpu-baseline > "$O/kstats_bench_${cfg}_$n.json" 2> "$O/kstats_${cfg}_$n.err" ;;
+        python bench.py --full --config "$cfg" --no-cpu-baseline > "$O/kstats_bench_${cfg}_$n.json" 2> "$O/kstats_${cfg}_$n.err" ;;
     pmc)
       run 120 "pmc $a1 $a2" rocprofv3 --pmc ${a3//,/ } -d "$O/pmc_${a1}_${a2}" -o run --output-format csv -- \
         python tools/run_steps.py --config "$a1" --steps 3 > "$O/pmc_${a1}_${a2}.log" 2>&1 ;;

@@ -3,8 +3,8 @@
 #   1. HBM traffic PMC passes (FETCH_SIZE, WRITE_SIZE; separate passes, no tracing domains) and an SQ
 #      instruction-count pass (VALU, SALU, transcendental), per config
 #   2. profiles/pmc_traffic.json and profiles/pmc_insts.json (keyed by config) for bench.py's roofline
-#   3. the bench.py line of each config (its roofline reads the two files just written)
-#   4. rocprofv3 --kernel-trace --stats over the default (cfg3) bench.py command (kernel averages must agree)
+#   3. the bench.py --full line of each config (its roofline reads the two files just written)
+#   4. rocprofv3 --kernel-trace --stats over the default (cfg3) bench.py --full command (kernel averages must agree)
 # Usage: tools/gpu_round_profile.sh TAG [CONFIGS...]   (default configs: cfg3 cfg2 cfg5)
 set -euo pipefail
 TAG=${1:-r3}
@@ -28,9 +28,9 @@ done
 cp profiles/pmc_traffic.json "$OUT/pmc_traffic.json"
 cp profiles/pmc_insts.json "$OUT/pmc_insts.json"
 for c in $CONFIGS; do
-  timeout -k 10 400 python bench.py --config $c > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"
+  timeout -k 10 400 python bench.py --full --config $c > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"
   echo "bench $c done"
 done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/kstats" -o run --output-format csv -- \
-  python bench.py --no-cpu-baseline > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.err"
+  python bench.py --full --no-cpu-baseline > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.err"
 echo done
