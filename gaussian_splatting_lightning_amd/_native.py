@@ -12,9 +12,9 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgsrast.so")
-ABI_VERSION = 2  # include/gsrast.h GSR_ABI_VERSION
+ABI_VERSION = 3  # include/gsrast.h GSR_ABI_VERSION
 
-GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_BWD_SCRATCH = 0, 1, 2, 3
+GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_BWD_SCRATCH, GSR_BUF_CAMERA_PARTIALS = 0, 1, 2, 3, 4
 
 _fp = ctypes.c_void_p  # device pointers are passed as integers
 
@@ -46,6 +46,7 @@ class BackwardArgs(ctypes.Structure):
         ("densify_accumulate", ctypes.c_int), ("max_radii2D", _fp),
         ("stages", ctypes.c_int), ("g_begin", ctypes.c_int64), ("g_end", ctypes.c_int64), ("bwd_scratch", _fp),
         ("campos_rows", _fp), ("campos_rank", ctypes.c_int), ("campos_nrows", ctypes.c_int),
+        ("dL_dviewmatrix", _fp), ("dL_dprojmatrix", _fp), ("dL_dcampos", _fp),
     ]
 
 

@@ -767,13 +767,28 @@ static bool zero_fill_plan(const gsr_backward_args *a, int64_t g0, int64_t g1, R
     return true;
 }
 
+// The camera gradients (dL_dviewmatrix / dL_dprojmatrix / dL_dcampos): written by the per-Gaussian stage
+static bool camera_grads(const gsr_backward_args *a) {
+    return a->stages != GSR_BWD_COMPOSITE && (a->dL_dviewmatrix || a->dL_dprojmatrix || a->dL_dcampos);
+}
+static int zero_camera_grads(const gsr_backward_args *a, hipStream_t stream) {  // no Gaussian: the empty sum
+    if (a->dL_dviewmatrix) GSR_HIP(hipMemsetAsync(a->dL_dviewmatrix, 0, sizeof(float) * 16, stream));
+    if (a->dL_dprojmatrix) GSR_HIP(hipMemsetAsync(a->dL_dprojmatrix, 0, sizeof(float) * 16, stream));
+    if (a->dL_dcampos) GSR_HIP(hipMemsetAsync(a->dL_dcampos, 0, sizeof(float) * 3, stream));
+    return GSR_OK;
+}
+
 int gsr_backward(const gsr_backward_args *a, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr) {
     if (!a || !alloc) return fail(GSR_ERR_ARG, "null argument");
     int rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
                           a->scales, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
                           a->background);
     if (rc) return rc;
-    if (a->P == 0) return GSR_OK;
+    if (a->P == 0) {
+        if (!camera_grads(a)) return GSR_OK;
+        StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+        return zero_camera_grads(a, (hipStream_t)stream_ptr);
+    }
     if (!a->dL_dpix || !a->radii) return fail(GSR_ERR_ARG, "dL_dpix and radii are required");
     if (!a->geom_buffer || !a->image_buffer || (a->R > 0 && !a->binning_buffer))
         return fail(GSR_ERR_ARG, "forward buffers are required");
@@ -896,7 +911,15 @@ int gsr_backward(const gsr_backward_args *a, gsr_alloc_fn alloc, void *alloc_ctx
         GSR_HIP(hipMemsetAsync(a->dL_dsh, 0, sizeof(float) * ng * a->M * 3, stream));
     if (pp.shs == nullptr && a->dL_dcolors_sh)
         GSR_HIP(hipMemsetAsync(a->dL_dcolors_sh, 0, sizeof(float) * ng * 3, stream));
-    GSR_STAGE(ST_PREPROCESS_BWD, dbg, launch_preprocess_bwd(stream, pp));
+    if (camera_grads(a)) {
+        if (ng == 0) return zero_camera_grads(a, stream);
+        pp.cam_partials = reinterpret_cast<float *>(alloc(alloc_ctx, GSR_BUF_CAMERA_PARTIALS, camera_partials_bytes((int64_t)ng)));
+        if (!pp.cam_partials) return fail(GSR_ERR_ALLOC, "camera partials allocation failed");
+    }
+    GSR_STAGE(ST_PREPROCESS_BWD, dbg, {
+        launch_preprocess_bwd(stream, pp);
+        if (pp.cam_partials) launch_camera_reduce(stream, pp, a->dL_dviewmatrix, a->dL_dprojmatrix, a->dL_dcampos);
+    });
     return GSR_OK;
 }
 

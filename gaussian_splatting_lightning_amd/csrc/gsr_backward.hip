@@ -59,18 +59,6 @@ struct ZeroFillAtExit {
 constexpr int BWD_BATCH = 32;
 constexpr int PART = 12;  // floats per instance in the LDS partial buffer (10 sums + 2 pad)
 
-// x + y after v_permlane32_swap(x, y): lanes 0-31 hold x[l] + x[l+32], lanes 32-63 hold y[l-32] + y[l]
-// (lane mapping measured on MI355X by tools/probes/permlane_probe.hip).
-__device__ __forceinline__ float sum_swap32(float x, float y) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// x + y after v_permlane16_swap(x, y): even rows hold x summed over the row pair, odd rows hold y.
-__device__ __forceinline__ float sum_swap16(float x, float y) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
 __device__ constexpr float kZero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 // Two instances: the bit-5 exchange pairs each raw sum of instance 0 with the same sum of instance 1 (7 swaps, not

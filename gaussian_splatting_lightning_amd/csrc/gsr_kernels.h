@@ -246,8 +246,14 @@ struct PreprocessBwdParams {
     float *campos_rows;      // (campos_nrows, 3): campos in row campos_rank, zeros elsewhere (may be null)
     int campos_rank, campos_nrows;
     int prezeroed = 0;       // the outputs were zero-filled (RenderBwdParams::zf_*): store only non-zero gradients
+    // camera gradients: camera_partials_bytes(g1 - g0) of per-wave partial sums (null: the kernels without them)
+    float *cam_partials = nullptr;
 };
 void launch_preprocess_bwd(hipStream_t s, const PreprocessBwdParams &p);
+// dL/dviewmatrix (16), dL/dprojmatrix (16), dL/dcampos (3) over Gaussians [g0, g1), each fully written or null: the
+// fixed-order sum of the partials launch_preprocess_bwd left in p.cam_partials (g1 > g0)
+size_t camera_partials_bytes(int64_t n);
+void launch_camera_reduce(hipStream_t s, const PreprocessBwdParams &p, float *dview, float *dproj, float *dcampos);
 
 // ---- multi-view SH gradient (gsr_views.hip) ----
 void launch_sh_backward_views(hipStream_t s, int P, int D, int M, int V, int chunk_len, const float *means3D,

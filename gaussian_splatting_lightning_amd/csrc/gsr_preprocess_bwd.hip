@@ -68,11 +68,14 @@ __device__ __forceinline__ PbwdCamera load_camera(const PreprocessBwdParams &p) 
     c.campos = (p.shs && p.M > 0) ? make_float3(p.campos[0], p.campos[1], p.campos[2]) : make_float3(0, 0, 0);
     return c;
 }
-template <bool LDS>
+// CAM: the Gaussian's 27 camera-gradient contributions go to cg (CAM_* layout); cg is left untouched (the caller's
+// zeros) on every path that ends before they are formed: culled, zeroed, out of range.
+constexpr int CAM_VIEW = 0, CAM_PROJ = 12, CAM_POS = 24, CAM_N = 27, CAM_SLOT = 32;
+template <bool LDS, bool CAM = false>
 __device__ __forceinline__ void preprocess_bwd_one(const PreprocessBwdParams &p, const PbwdCamera &cam, const int i,
                                                    const int radius, const uint32_t n_tiles, bool have_gs,
                                                    const float (&gs_in)[10], float3 &dRGB_out, float3 &dir_out,
-                                                   bool &zeroed) {
+                                                   bool &zeroed, float (&cg)[CAM_N]) {
     // radius and kept-tile count: the caller's loads (reloaded here they took a round trip of their own)
     const bool vis = radius > 0;
     // The densification statistics' read-modify-writes: the reads issued here, the writes at the end (put_stats).
@@ -260,6 +263,25 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreprocessBwdParams &p,
     if (p.has_invdepth) dtz -= gs[9] / (t.z * t.z);
     float3 dm = make_float3(vm[0] * dtx + vm[1] * dty + vm[2] * dtz, vm[4] * dtx + vm[5] * dty + vm[6] * dtz,
                             vm[8] * dtx + vm[9] * dty + vm[10] * dtz);
+    if constexpr (CAM) {
+        // dL/dviewmatrix[r][c], c < 3: through t = (mean, 1) V, and through W = V[:3,:3]^T in T = J W
+        // (T0[k] = J00 vm[4k] + J02 vm[4k+2], T1[k] = J11 vm[4k+1] + J12 vm[4k+2], J of the clamped t as in ewa_T)
+        const float j00 = hx * tz, j11 = hy * tz, j02 = -(hx * t.x) * tz2, j12 = -(hy * t.y) * tz2;
+        // Outside the 1.3 tan(fov) clamp the clamped t.x is a constant times t.z, so d J02 / d t.z is hx t.x / t.z^3:
+        // the derivative of the clamp as written, which the camera gradients follow (those of autograd through the
+        // reference).  dtz above keeps the upstream convention for dL/dmeans3D (twice that, t.x taken as constant).
+        const float dtz_c = dtz - (1.f - e.xmul) * (hx * t.x) * tz3 * dJ02 - (1.f - e.ymul) * (hy * t.y) * tz3 * dJ12;
+        const float m3[3] = {mean.x, mean.y, mean.z};
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            cg[CAM_VIEW + 3 * r] = m3[r] * dtx + j00 * dT0[r];
+            cg[CAM_VIEW + 3 * r + 1] = m3[r] * dty + j11 * dT1[r];
+            cg[CAM_VIEW + 3 * r + 2] = m3[r] * dtz_c + j02 * dT0[r] + j12 * dT1[r];
+        }
+        cg[CAM_VIEW + 9] = dtx;
+        cg[CAM_VIEW + 10] = dty;
+        cg[CAM_VIEW + 11] = dtz_c;
+    }
     // ---- 2D mean -> 3D mean through the projection ----
     const Mat4 &proj = cam.proj;
     const float *pm = proj.m;
@@ -271,6 +293,17 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreprocessBwdParams &p,
     dm.x += (pm[0] * m_w - pm[3] * mul1) * g2x + (pm[1] * m_w - pm[3] * mul2) * g2y;
     dm.y += (pm[4] * m_w - pm[7] * mul1) * g2x + (pm[5] * m_w - pm[7] * mul2) * g2y;
     dm.z += (pm[8] * m_w - pm[11] * mul1) * g2x + (pm[9] * m_w - pm[11] * mul2) * g2y;
+    if constexpr (CAM) {
+        // dL/dprojmatrix[r][c], c in {0, 1, 3}: mh = (mean, 1) P, the 2D mean is (mh.x, mh.y) / (mh.w + 1e-7);
+        // mul1 / mul2 are mh.x / mh.y times m_w^2.  (mh.x and mh.y themselves stay unused, as without CAM: they are
+        // formed without FMA contraction, and sharing their products would take the contraction from mul1 / mul2)
+        const float dmh[3] = {g2x * m_w, g2y * m_w, -(mul1 * g2x + mul2 * g2y)};
+        const float m4[4] = {mean.x, mean.y, mean.z, 1.f};
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) cg[CAM_PROJ + 3 * r + c] = m4[r] * dmh[c];
+    }
     // ---- SH backward ----
     // dL/dsh = basis(dir) (x) dRGB needs only the direction; the direction term of dL/dmeans3D uses the colour's
     // direction Jacobian the forward stored (sh_jac), so the 48 coefficients are not read here.  (The backward's
@@ -285,12 +318,16 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreprocessBwdParams &p,
         float *dsh = p.dL_dsh ? p.dL_dsh + (size_t)i * ncoef : nullptr;  // null only with dL_dcolors_sh (API)
         if (LDS) {
             // LDS-staged block (M = 16): the kernel writes dL/dsh = basis (x) dRGB through LDS
-            dm = dm + sh_dir_grad(mean - campos, dRGB, jx, jy, jz);
+            const float3 dd = sh_dir_grad(mean - campos, dRGB, jx, jy, jz);
+            dm = dm + dd;
+            if constexpr (CAM) { cg[CAM_POS] = -dd.x; cg[CAM_POS + 1] = -dd.y; cg[CAM_POS + 2] = -dd.z; }
             dRGB_out = dRGB;
             dir_out = mean - campos;
         } else {
             float dshv[48];
-            dm = dm + sh_backward_jac_dispatch(p.D, mean - campos, dRGB, jx, jy, jz, dshv);
+            const float3 dd = sh_backward_jac_dispatch(p.D, mean - campos, dRGB, jx, jy, jz, dshv);
+            dm = dm + dd;
+            if constexpr (CAM) { cg[CAM_POS] = -dd.x; cg[CAM_POS + 1] = -dd.y; cg[CAM_POS + 2] = -dd.z; }
             if (dsh && p.sh_vec16) {
                 float4 *d4 = reinterpret_cast<float4 *>(dsh);
 #pragma unroll
@@ -350,6 +387,32 @@ __device__ __forceinline__ void zero_gaussian_stats(const PreprocessBwdParams &p
     }
     if (p.max_radii2D) p.max_radii2D[i] = max(p.max_radii2D[i], radius);
 }
+// The wave's sums of the 27 camera contributions, to its own partial slot (CAM_SLOT floats, words CAM_N.. zero).  A transposing reduction: every level halves the values a lane holds while it adds one lane bit,
+// so the 27 sums cost 14 + 7 lane swaps and 8 DPP adds instead of 27 x 6 adds.  After the bit-5 swaps a[k] is value
+// 2 k + b5, after the bit-4 swaps b[k] is value 4 k + 2 b4 + b5, and so on down to one value per lane pair,
+// 16 b1 + 8 b2 + 4 b3 + 2 b4 + b5 (row_half_mirror pairs lane l with 7 - l: the partner differs in bit 2, and the
+// quad bits it also flips are summed over by the levels after it).  Every lane of the wave must be active; no block
+// barrier, so it may follow the waves' early returns.  The order of the additions is fixed by the lane numbers alone.
+__device__ __forceinline__ void cam_wave_store(const float (&cg)[CAM_N], float *__restrict__ slot, const int lane) {
+    float a[16], b[8], c[4], d[2];
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+        a[k] = 2 * k < CAM_N ? sum_swap32(cg[min(2 * k, CAM_N - 1)], 2 * k + 1 < CAM_N ? cg[min(2 * k + 1, CAM_N - 1)] : 0.f) : 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) b[k] = 4 * k < CAM_N ? sum_swap16(a[2 * k], a[2 * k + 1]) : 0.f;
+    const bool hi3 = (lane & 8) != 0, hi2 = (lane & 4) != 0, hi1 = (lane & 2) != 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        c[k] = dpp_xadd<0x128>(hi3 ? b[2 * k + 1] : b[2 * k], hi3 ? b[2 * k] : b[2 * k + 1]);  // row_ror:8 (= lane ^ 8)
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+        d[k] = dpp_xadd<0x141>(hi2 ? c[2 * k + 1] : c[2 * k], hi2 ? c[2 * k] : c[2 * k + 1]);  // row_half_mirror
+    float e = dpp_xadd<0x4E>(hi1 ? d[1] : d[0], hi1 ? d[0] : d[1]);                            // quad_perm [2,3,0,1]
+    e = dpp_add<0xB1>(e);                                                                      // quad_perm [1,0,3,2]
+    const int v = ((lane & 2) << 3) | ((lane & 4) << 1) | ((lane & 8) >> 1) | ((lane & 16) >> 3) | ((lane & 32) >> 5);
+    if (!(lane & 1)) slot[v] = e;  // all CAM_SLOT words (the sums of the padding are zero)
+}
+template <bool CAM>
 __device__ __forceinline__ void compacted_tail(const PreprocessBwdParams &p, const PbwdCamera &cam, const int i,
                                                const int rad, const uint32_t cnt, const bool has_rows,
                                                const float (&gs)[10], float *sw, const int w, const int lane) {
@@ -398,10 +461,16 @@ __device__ __forceinline__ void compacted_tail(const PreprocessBwdParams &p, con
 #pragma unroll
     for (int k = 0; k < 10; k++) gse[k] = has ? list[(2 + k) * 256 + e] : 0.f;
     __syncthreads();  // the list is consumed: the areas are the waves' staging areas again
-    if ((uint32_t)(w * 64) >= total) return;  // wave-uniform: no entry for this wave
+    if ((uint32_t)(w * 64) >= total) {  // wave-uniform: no entry for this wave
+        if constexpr (CAM)  // (its partial slot is read all the same)
+            if (lane < CAM_SLOT) p.cam_partials[(size_t)(blockIdx.x * 4 + w) * CAM_SLOT + lane] = 0.f;
+        return;
+    }
     float3 dRGB = make_float3(0.f, 0.f, 0.f), dir = make_float3(1.f, 0.f, 0.f);
     bool zg = false;
-    if (has) preprocess_bwd_one<true>(p, cam, ge, rade, cnte, true, gse, dRGB, dir, zg);
+    float cg[CAM_N] = {};
+    if (has) preprocess_bwd_one<true, CAM>(p, cam, ge, rade, cnte, true, gse, dRGB, dir, zg, cg);
+    if constexpr (CAM) cam_wave_store(cg, p.cam_partials + (size_t)(blockIdx.x * 4 + w) * CAM_SLOT, lane);
     if (!p.dL_dsh) return;
     const uint64_t live = __ballot(has && !zg);  // (a big Gaussian whose sum is zero stays zero-filled)
 #pragma unroll
@@ -421,7 +490,9 @@ __device__ __forceinline__ void compacted_tail(const PreprocessBwdParams &p, con
         }
     }
 }
-template <bool LDS_SH, bool COMPACT = false>  // COMPACT: p.prezeroed (compacted_tail)
+// CAM: the camera gradients' per-wave partial sums as well (p.cam_partials: every wave of the launch writes its slot
+// on every path, so the finishing pass reads nothing stale), a compile-time variant so the kernels without them keep their registers
+template <bool LDS_SH, bool COMPACT = false, bool CAM = false>  // COMPACT: p.prezeroed (compacted_tail)
 __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdParams p) {
     const int i = p.g0 + blockIdx.x * 256 + threadIdx.x;
     const PbwdCamera cam = load_camera(p);  // before the first store (scalar loads)
@@ -431,11 +502,14 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdParams
     if (!LDS_SH) {
         const float none[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         float3 d3, v3;
+        float cg[CAM_N] = {};
         if (i < p.g1) {
             const int rad = p.radii[i];
             bool zg = false;
-            preprocess_bwd_one<false>(p, cam, i, rad, rad > 0 ? p.tiles[i] : 0u, false, none, d3, v3, zg);
+            preprocess_bwd_one<false, CAM>(p, cam, i, rad, rad > 0 ? p.tiles[i] : 0u, false, none, d3, v3, zg, cg);
         }
+        if constexpr (CAM)
+            cam_wave_store(cg, p.cam_partials + (size_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * CAM_SLOT, threadIdx.x & 63);
         return;
     }
     __shared__ __attribute__((aligned(16))) float s_sh[4][PBWD_STAGE];
@@ -527,10 +601,12 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdParams
     float3 dRGB = make_float3(0.f, 0.f, 0.f), dir = make_float3(1.f, 0.f, 0.f);
     bool zg = false;
     if constexpr (COMPACT) {
-        compacted_tail(p, cam, i, rad, cnt, live, gs, sw, w, lane);
+        compacted_tail<CAM>(p, cam, i, rad, cnt, live, gs, sw, w, lane);
         return;
     }
-    if (i < p.g1) preprocess_bwd_one<true>(p, cam, i, rad, cnt, true, gs, dRGB, dir, zg);
+    float cg[CAM_N] = {};
+    if (i < p.g1) preprocess_bwd_one<true, CAM>(p, cam, i, rad, cnt, true, gs, dRGB, dir, zg, cg);
+    if constexpr (CAM) cam_wave_store(cg, p.cam_partials + (size_t)(blockIdx.x * 4 + w) * CAM_SLOT, lane);
     if (!p.dL_dsh) return;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
@@ -548,17 +624,75 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdParams
     }
 }
 
-void launch_preprocess_bwd(hipStream_t s, const PreprocessBwdParams &p) {
-    if (p.g1 <= p.g0) return;
-    const uint32_t grid = div_up((uint32_t)(p.g1 - p.g0), 256);
+// Fixed-order sum of the camera partial slots: block b adds slots [b G, min(n, (b + 1) G)) -- lane group q the slots
+// q, q + 8, ... of the range in turn, then the eight groups in order -- into slot b of `out`, or, as the last level
+// (out null), into the three gradients with their structural zeros (column 3 of the view matrix, column 2 of the
+// projection matrix).  Which slots meet in which addition depends on (n, G) alone.
+constexpr uint32_t CAM_GROUP = 256;  // slots per block of the first level (32 KB)
+__global__ __launch_bounds__(256) void camera_reduce_kernel(const float *__restrict__ in, const uint32_t n, const uint32_t G,
+                                                            float *__restrict__ out, float *__restrict__ dview,
+                                                            float *__restrict__ dproj, float *__restrict__ dcampos) {
+    __shared__ float s_part[8][CAM_SLOT];
+    const uint32_t k = threadIdx.x & 31, q = threadIdx.x >> 5;
+    const uint32_t j0 = blockIdx.x * G, j1 = min(n, j0 + G);
+    float acc = 0.f;
+    for (uint32_t j = j0 + q; j < j1; j += 8) acc += in[(size_t)j * CAM_SLOT + k];
+    s_part[q][k] = acc;
+    __syncthreads();  // reached by all 256 threads
+    if (threadIdx.x >= 32) return;
+    float t = 0.f;
+#pragma unroll
+    for (int g = 0; g < 8; g++) t += s_part[g][k];
+    if (out) {
+        out[(size_t)blockIdx.x * CAM_SLOT + k] = t;
+    } else if (k < CAM_PROJ) {
+        if (dview) dview[4 * (k / 3) + k % 3] = t;
+    } else if (k < CAM_POS) {
+        const uint32_t e = k - CAM_PROJ, c = e % 3;
+        if (dproj) dproj[4 * (e / 3) + (c == 2 ? 3 : c)] = t;
+    } else if (k < CAM_N) {
+        if (dcampos) dcampos[k - CAM_POS] = t;
+    } else if (k < CAM_N + 4) {
+        if (dview) dview[4 * (k - CAM_N) + 3] = 0.f;
+        if (dproj) dproj[4 * (k - CAM_N) + 2] = 0.f;
+    }
+}
+
+// slots of the launch over n Gaussians (one per wave), and of the first reduction level behind them
+static uint32_t cam_slots(int64_t n) { return div_up((uint32_t)n, 256) * 4; }
+size_t camera_partials_bytes(int64_t n) {
+    const uint32_t slots = cam_slots(n);
+    return sizeof(float) * CAM_SLOT * ((size_t)slots + div_up(slots, CAM_GROUP));
+}
+
+void launch_camera_reduce(hipStream_t s, const PreprocessBwdParams &p, float *dview, float *dproj, float *dcampos) {
+    const uint32_t slots = cam_slots(p.g1 - p.g0), n1 = div_up(slots, CAM_GROUP);
+    float *lvl1 = p.cam_partials + (size_t)slots * CAM_SLOT;
+    if (n1 > 1) {
+        camera_reduce_kernel<<<n1, 256, 0, s>>>(p.cam_partials, slots, CAM_GROUP, lvl1, nullptr, nullptr, nullptr);
+        camera_reduce_kernel<<<1, 256, 0, s>>>(lvl1, n1, n1, nullptr, dview, dproj, dcampos);
+    } else {
+        camera_reduce_kernel<<<1, 256, 0, s>>>(p.cam_partials, slots, CAM_GROUP, nullptr, dview, dproj, dcampos);
+    }
+}
+
+template <bool CAM>
+static void launch_preprocess_bwd_t(hipStream_t s, const PreprocessBwdParams &p, const uint32_t grid) {
     // the joint row gather and the LDS-staged dL/dsh stores; without dL/dsh (the compact multi-view exchange) only
     // the gather, which the per-lane path pays ~40 % of the kernel for
     if ((p.dL_dsh ? p.sh_vec16 : true) && tuning("pbwd_lds_sh", 1) && p.prezeroed)
-        preprocess_bwd_kernel<true, true><<<grid, 256, 0, s>>>(p);
+        preprocess_bwd_kernel<true, true, CAM><<<grid, 256, 0, s>>>(p);
     else if ((p.dL_dsh ? p.sh_vec16 : true) && tuning("pbwd_lds_sh", 1))
-        preprocess_bwd_kernel<true><<<grid, 256, 0, s>>>(p);
+        preprocess_bwd_kernel<true, false, CAM><<<grid, 256, 0, s>>>(p);
     else
-        preprocess_bwd_kernel<false><<<grid, 256, 0, s>>>(p);
+        preprocess_bwd_kernel<false, false, CAM><<<grid, 256, 0, s>>>(p);
+}
+
+void launch_preprocess_bwd(hipStream_t s, const PreprocessBwdParams &p) {
+    if (p.g1 <= p.g0) return;
+    const uint32_t grid = div_up((uint32_t)(p.g1 - p.g0), 256);
+    if (p.cam_partials) launch_preprocess_bwd_t<true>(s, p, grid);  // every wave writes its whole slot, on every path
+    else launch_preprocess_bwd_t<false>(s, p, grid);
 }
 
 }  // namespace gsr

@@ -6,7 +6,8 @@ Mirrors the reference's pure-Python module interface (gs_lightning/rasterize/__i
   tanfovx, tanfovy, viewmatrix, projmatrix, campos, background, sh_degree)`` -> ``(image (3,H,W), radii (N,)
   float, invdepth (1,H,W))`` -- same argument order and meaning as gs_lightning/rasterize/rasterize.py:28-46,
   same return layout as :125-127 (radii are returned as float, as the Python path does at :79-80).
-  Differentiable w.r.t. means3D, opacities, scales, rotations and shs.
+  Differentiable w.r.t. means3D, opacities, scales, rotations and shs, and w.r.t. viewmatrix, projmatrix and campos
+  as three independent inputs where they require grad (as autograd through the reference's Python path).
 * ``markVisible(means3D, viewmatrix, projmatrix)`` -> bool (N,) (rasterize.py:23-26).
 
 Compositing follows the CUDA submodule's semantics: the Python path's per-tile

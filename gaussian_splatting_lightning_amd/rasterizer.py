@@ -172,7 +172,7 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
 
 
 def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_depth=None, out=None,
-                 compact_sh=False, accumulate_stats=False):
+                 compact_sh=False, accumulate_stats=False, camera_grads=False):
     """One call of gsr_backward.  Returns a dict of gradients (means3D, means2D, shs, colors_precomp,
     opacities, scales, rotations, cov3D_precomp); entries are None where the input was absent.
     `out` may supply preallocated contiguous float32 destinations (e.g. views into one flat buffer that is
@@ -183,7 +183,10 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     accumulate_stats=True adds this view's densify_stats to out["densify_stats"] (the reference's
     add_densification_stats); out["max_radii2D"] is always max-accumulated with this view's radii.
     compact_sh=True skips dL/dshs and returns the clamp-masked colour gradient "colors_sh" instead -- the
-    per-view factor that `sh_backward_views` expands after an all-gather (multiview.py)."""
+    per-view factor that `sh_backward_views` expands after an all-gather (multiview.py).
+    camera_grads=True adds the gradients of the camera, as three independent inputs: viewmatrix (4,4) (column 3
+    zero), projmatrix (4,4) (column 2 zero) and campos (3) (zero without SH colours); `out` may supply them under
+    those names.  Deterministic sums over the Gaussians; the other gradients are bitwise what they are without."""
     lib = _native.load()
     rs = raster_settings
     st = state
@@ -222,6 +225,9 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     dscales = dst("scales", P, 3)
     drot = dst("rotations", P, 4)
     cam_rows, cam_rank, cam_n = _campos_rows(out.get("campos_rows"))
+    dview = dst("viewmatrix", 4, 4) if camera_grads else None
+    dproj = dst("projmatrix", 4, 4) if camera_grads else None
+    dcampos = dst("campos", 3) if camera_grads else None
     bufs = _Buffers(device)
     a = _native.BackwardArgs(
         P=P, D=int(rs.sh_degree), M=M, W=W, H=H, R=st.num_rendered, num_big=st.num_big, background=_ptr(st.bg),
@@ -236,12 +242,15 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
         dL_dmeans3D=dmeans3D.data_ptr(), dL_dcov3D=_ptr(dcov), dL_dsh=_ptr(dsh),
         dL_dscales=dscales.data_ptr(), dL_drotations=drot.data_ptr(), dL_dcolors_sh=_ptr(dcsh),
         densify_stats=_ptr(dstats), densify_accumulate=int(bool(accumulate_stats)), max_radii2D=_ptr(mrad),
-        campos_rows=cam_rows, campos_rank=cam_rank, campos_nrows=cam_n)
+        campos_rows=cam_rows, campos_rank=cam_rank, campos_nrows=cam_n,
+        dL_dviewmatrix=_ptr(dview), dL_dprojmatrix=_ptr(dproj), dL_dcampos=_ptr(dcampos))
     with torch.cuda.device(device):
         rc = lib.gsr_backward(ctypes.byref(a), bufs.callback, None, _stream_handle(device))
     bufs.raise_pending()
     _native.check(rc, "rasterize_gaussians_backward")
+    camera = dict(viewmatrix=dview, projmatrix=dproj, campos=dcampos) if camera_grads else {}
     return dict(
+        **camera,
         means3D=dmeans3D, means2D=dmeans2D,
         shs=dsh.view_as(st.shs) if (st.shs is not None and dsh is not None) else None, colors_sh=dcsh,
         colors_precomp=dcolors if st.colors_precomp is not None else None,
@@ -260,7 +269,9 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
 
     chunks: list of (g_begin, g_end, out) with out a dict of destinations for those Gaussians only (same keys and
     row widths as backward_raw's `out`, (g_end - g_begin) rows each, contiguous float32; max_radii2D int32).
-    Results are bitwise those of one backward_raw call: every Gaussian is computed by the same code."""
+    Results are bitwise those of one backward_raw call: every Gaussian is computed by the same code.
+    A chunk's out may also hold viewmatrix (4,4), projmatrix (4,4) and campos (3): the camera gradients summed over
+    that chunk's Gaussians (the caller adds the chunks; each chunk needs its own destinations)."""
     lib = _native.load()
     rs = raster_settings
     st = state
@@ -295,6 +306,11 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
             for name, t in out.items():
                 if name == "campos_rows":
                     continue
+                if name in _CAMERA_SHAPES:
+                    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != _CAMERA_SHAPES[name]:
+                        raise RuntimeError(f"chunk {k}: out[{name!r}] must be a contiguous float32 tensor of shape "
+                                           f"{_CAMERA_SHAPES[name]}")
+                    continue
                 want = (torch.int32, (n,)) if name == "max_radii2D" else (torch.float32, None)
                 if t.dtype != want[0] or not t.is_contiguous() or t.shape[0] != n or (
                         name in widths and t.numel() != n * widths[name]):
@@ -309,12 +325,17 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
                 dL_dscales=_ptr(out.get("scales")), dL_drotations=_ptr(out.get("rotations")),
                 dL_dcolors_sh=_ptr(out.get("colors_sh")), densify_stats=_ptr(out.get("densify_stats")),
                 max_radii2D=_ptr(out.get("max_radii2D")), campos_rows=cam_rows, campos_rank=cam_rank,
-                campos_nrows=cam_n, **base)
+                campos_nrows=cam_n, dL_dviewmatrix=_ptr(out.get("viewmatrix")),
+                dL_dprojmatrix=_ptr(out.get("projmatrix")), dL_dcampos=_ptr(out.get("campos")), **base)
             rc = lib.gsr_backward(ctypes.byref(a), bufs.callback, None, _stream_handle(device))
+            bufs.raise_pending()
             _native.check(rc, f"rasterize_gaussians_backward (chunk {k})")
             if on_chunk is not None:
                 on_chunk(k)
     return scratch
+
+
+_CAMERA_SHAPES = dict(viewmatrix=(4, 4), projmatrix=(4, 4), campos=(3,))
 
 
 def _campos_rows(spec):
@@ -332,10 +353,13 @@ def _campos_rows(spec):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
+                raster_settings, *camera):
+        # camera: () or the settings' (viewmatrix, projmatrix, campos) once more, as inputs autograd can hand a
+        # gradient to (rasterize_gaussians); the values are read from the settings either way
         color, radii, invdepth, st = forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations,
                                                  cov3Ds_precomp, raster_settings)
         ctx.raster_settings = raster_settings
+        ctx.camera = [(tuple(t.shape), t.device) for t in camera]
         ctx.meta = (st.num_rendered, st.num_big, st.M)
         ctx.present = tuple(t is not None for t in st)
         empty = torch.empty(0, device=means3D.device)
@@ -348,8 +372,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         saved = ctx.saved_tensors
         tensors = [t if present else None for t, present in zip(saved, ctx.present[:15])]
         st = ForwardState(*tensors, *ctx.meta)
-        g = backward_raw(st, ctx.raster_settings, grad_out_color, grad_out_depth)
         need = ctx.needs_input_grad
+        g = backward_raw(st, ctx.raster_settings, grad_out_color, grad_out_depth, camera_grads=any(need[9:]))
+        camera = tuple(g[name].reshape(shape).to(dev) if wanted else None for name, (shape, dev), wanted in
+                       zip(("viewmatrix", "projmatrix", "campos"), ctx.camera, need[9:]))
         return (g["means3D"] if need[0] else None,
                 g["means2D"] if need[1] else None,
                 g["shs"] if need[2] else None,
@@ -358,13 +384,21 @@ class _RasterizeGaussians(torch.autograd.Function):
                 g["scales"] if need[5] else None,
                 g["rotations"] if need[6] else None,
                 g["cov3D_precomp"] if need[7] else None,
-                None)
+                None, *camera)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings):
+    """Differentiable with respect to the Gaussians' tensors and, where raster_settings.viewmatrix, .projmatrix or
+    .campos requires grad, to those three as independent inputs (projmatrix being the full view-projection product:
+    a caller optimising a pose builds projmatrix and campos from its view matrix in torch, which chains the three)."""
+    rs = raster_settings
+    camera = (rs.viewmatrix, rs.projmatrix, rs.campos)
+    if not (torch.is_grad_enabled() and all(torch.is_tensor(t) for t in camera)
+            and any(t.requires_grad for t in camera)):
+        camera = ()  # the call as it is without camera gradients
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings)
+                                     cov3Ds_precomp, raster_settings, *camera)
 
 
 def sh_backward_views(means3D: torch.Tensor, campos: torch.Tensor, dcolors_sh: torch.Tensor, sh_degree: int, M: int,

@@ -37,7 +37,13 @@ extern "C" {
  * valid until the caller frees it (the forward's three buffers must survive until the backward). */
 typedef char *(*gsr_alloc_fn)(void *ctx, int which, size_t nbytes);
 
-enum { GSR_BUF_GEOM = 0, GSR_BUF_BINNING = 1, GSR_BUF_IMAGE = 2, GSR_BUF_BWD_SCRATCH = 3 };
+enum {
+    GSR_BUF_GEOM = 0,
+    GSR_BUF_BINNING = 1,
+    GSR_BUF_IMAGE = 2,
+    GSR_BUF_BWD_SCRATCH = 3,
+    GSR_BUF_CAMERA_PARTIALS = 4 /* gsr_backward, only when a camera gradient is asked for; free after the call */
+};
 
 enum {
     GSR_OK = 0,
@@ -140,6 +146,19 @@ typedef struct gsr_backward_args {
      * SUM all-reduce of the block then yields every rank's camera).  NULL to skip. */
     float *campos_rows;
     int campos_rank, campos_nrows;
+    /* Camera gradients (GSR_ABI_VERSION 3), each NULL to skip and fully written otherwise: those of viewmatrix,
+     * projmatrix and campos as three independent inputs, in their own row-major layout.
+     *   dL_dviewmatrix (16): column 3 is zero (p_view = [p,1] @ V reads columns 0-2); the view-space point and the
+     *     rotation inside the EWA covariance projection both contribute.  Outside the 1.3 tan(fov) clamp of the EWA
+     *     Jacobian the clamp is differentiated as written (autograd's result), whereas dL_dmeans3D keeps the upstream
+     *     backward's convention there (the clamped coordinate taken as constant);
+     *   dL_dprojmatrix (16): column 2 is zero (the 2D mean reads x, y, w; depth comes from viewmatrix);
+     *   dL_dcampos (3): minus the sum of the SH view-direction term of dL_dmeans3D (zero with colors_precomp or M = 0).
+     * Sums over the Gaussians in a fixed order (per-wave partials in the caller's GSR_BUF_CAMERA_PARTIALS buffer, then
+     * a two-level tree whose shape depends only on the Gaussian range): no float atomics, bitwise reproducible.
+     * GSR_BWD_ALL writes the whole sums, GSR_BWD_GAUSSIANS those over [g_begin, g_end) (the caller adds the chunks),
+     * GSR_BWD_COMPOSITE ignores them; with P = 0 they are zero. */
+    float *dL_dviewmatrix, *dL_dprojmatrix, *dL_dcampos;
 } gsr_backward_args;
 
 enum { GSR_BWD_ALL = 0, GSR_BWD_COMPOSITE = 1, GSR_BWD_GAUSSIANS = 2 };
@@ -372,8 +391,10 @@ int gsr_stream_wait(void *stream, uint32_t *flag, uint32_t value);
 /* ABI version of this header.  2: gsr_state_layout gained struct_size at offset 0 and lost img_tile_sorted /
  * img_tile_lastkey (a one-time break: a caller built against a version-1 header reads shifted offsets, so it must
  * check gsr_abi_version() == GSR_ABI_VERSION before using the layout).  From version 2 on, fields of the versioned
- * structs are only appended, and callers built against this header or a later one interoperate. */
-#define GSR_ABI_VERSION 2
+ * structs are only appended, and callers built against this header or a later one interoperate.  3: gsr_backward_args,
+ * which carries no size field, gained dL_dviewmatrix / dL_dprojmatrix / dL_dcampos at its end (a version-2 caller's
+ * struct ends before them, so the library would read past it). */
+#define GSR_ABI_VERSION 3
 int gsr_abi_version(void);
 
 #ifdef __cplusplus
