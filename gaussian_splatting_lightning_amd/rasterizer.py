@@ -261,7 +261,7 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
 
 
 def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_out_depth, chunks, on_chunk=None,
-                     compact_sh=False, accumulate_stats=False):
+                     compact_sh=False, accumulate_stats=False, after_composite=None):
     """The backward split so that a gradient exchange overlaps it (multiview.py): ONE gsr_backward call for the
     compositing backward (GSR_BWD_COMPOSITE: instance gradient rows into a scratch buffer kept here), then one call
     per Gaussian chunk for the per-Gaussian stage (GSR_BWD_GAUSSIANS), each followed by on_chunk(k) -- which may
@@ -271,7 +271,8 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
     row widths as backward_raw's `out`, (g_end - g_begin) rows each, contiguous float32; max_radii2D int32).
     Results are bitwise those of one backward_raw call: every Gaussian is computed by the same code.
     A chunk's out may also hold viewmatrix (4,4), projmatrix (4,4) and campos (3): the camera gradients summed over
-    that chunk's Gaussians (the caller adds the chunks; each chunk needs its own destinations)."""
+    that chunk's Gaussians (the caller adds the chunks; each chunk needs its own destinations).
+    after_composite(), when given, runs between the compositing call and the first per-Gaussian call."""
     lib = _native.load()
     rs = raster_settings
     st = state
@@ -298,6 +299,8 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
         bufs.raise_pending()
         _native.check(rc, "rasterize_gaussians_backward (composite)")
         scratch = bufs.get(_native.GSR_BUF_BWD_SCRATCH)
+        if after_composite is not None:
+            after_composite()
         widths = dict(means2D=3, colors=3, opacities=1, means3D=3, cov3D=6, shs=3 * max(M, 0), scales=3, rotations=4,
                       colors_sh=3, densify_stats=2)
         for k, (g0, g1, out) in enumerate(chunks):

@@ -1220,3 +1220,38 @@ def test_second_backward_on_one_forward_sees_its_own_rows(gpu_device):
         assert np.array_equal(second[k], fresh[k]), k
         assert np.array_equal(unmarked[k], fresh[k]), k
         assert np.array_equal(third[k], fresh[k]), k
+
+
+def test_split_stage_backward_reads_the_live_flags_validity_word(gpu_device):
+    """The per-Gaussian pass trusts the live flags only when the LAST composite marked them (CNT_LIVE_VALID).  The
+    guarded situation needs split stages: after a marked backward on the same forward (whose upstream gradient is zero
+    on half the image, so its marks miss Gaussians the next one needs), GSR_BWD_COMPOSITE runs with "bwd_live" 0 --
+    it marks nothing and clears the validity word -- and GSR_BWD_GAUSSIANS then runs with "bwd_live" 1 and does read
+    the flags' pointer.  The result must be bitwise a fresh forward + backward."""
+    from gaussian_splatting_lightning_amd import _native
+    from gaussian_splatting_lightning_amd.rasterizer import backward_chunked, backward_raw, forward_raw
+    n, W, H = 20_000, 320, 240
+    inp = scene_inputs(n, W, H, sh_degree=3, seed=31, stress_fraction=0.01)
+    rs = settings_for(inp, gpu_device)
+    t = {k: torch.as_tensor(inp[k], device=gpu_device) for k in ("means3D", "opacities", "scales", "rotations", "shs")}
+    args = (t["means3D"], t["shs"], None, t["opacities"], t["scales"], t["rotations"], None, rs)
+    d1, i1 = (torch.as_tensor(a, device=gpu_device) for a in upstream(W, H, 31))
+    d2, i2 = (torch.as_tensor(a, device=gpu_device) for a in upstream(W, H, 32))
+    d1[:, :, W // 2:] = 0.0
+    i1[:, :, W // 2:] = 0.0
+    widths = dict(means3D=3, means2D=3, opacities=1, scales=3, rotations=4, shs=48)
+
+    _, _, _, st = forward_raw(*args)
+    backward_raw(st, rs, d1, i1)  # marks the left half's Gaussians
+    out = {k: torch.full((n, w), float("nan"), device=gpu_device) for k, w in widths.items()}
+    try:
+        _native.set_tuning("bwd_live", 0)  # the composite: no marks, validity word cleared
+        backward_chunked(st, rs, d2, i2, [(0, n, out)],
+                         after_composite=lambda: _native.set_tuning("bwd_live", 1))  # the per-Gaussian pass reads it
+    finally:
+        _native.unset_tuning("bwd_live")
+    _, _, _, st2 = forward_raw(*args)
+    fresh = backward_raw(st2, rs, d2, i2)
+    torch.cuda.synchronize()
+    for k in GRADS:
+        assert torch.equal(out[k].reshape(fresh[k].shape), fresh[k]), k
