@@ -51,6 +51,15 @@ class BackwardArgs(ctypes.Structure):
 
 
 GSR_BWD_ALL, GSR_BWD_COMPOSITE, GSR_BWD_GAUSSIANS = 0, 1, 2
+GSR_BUF_BACKGROUND_PARTIALS = 5
+
+
+class CompositeExt(ctypes.Structure):  # include/gsrast.h gsr_composite_ext (versioned by struct_size)
+    _fields_ = [("struct_size", ctypes.c_size_t), ("background_image", _fp), ("out_alpha", _fp), ("dL_dalpha", _fp),
+                ("dL_dbackground", _fp), ("dL_dbackground_image", _fp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=ctypes.sizeof(CompositeExt), **fields)
 
 
 class AdamGroup(ctypes.Structure):
@@ -115,6 +124,7 @@ EXPORTED_SYMBOLS = (
     "gsr_activations_forward", "gsr_activations_backward",
     "gsr_densify_workspace_bytes", "gsr_densify_classify", "gsr_densify_apply", "gsr_ply_unpack", "gsr_ply_pack",
     "gsr_knn_workspace_bytes", "gsr_knn_mean_dist2", "gsr_debug_wave_stamps",
+    "gsr_forward_ext", "gsr_backward_ext",
 )
 
 _lib = None
@@ -136,6 +146,13 @@ def load(path: str | None = None):
     lib.gsr_forward.restype = ctypes.c_int
     lib.gsr_backward.argtypes = [ctypes.POINTER(BackwardArgs), ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p]
     lib.gsr_backward.restype = ctypes.c_int
+    if hasattr(lib, "gsr_forward_ext"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
+        lib.gsr_forward_ext.argtypes = [ctypes.POINTER(ForwardArgs), ctypes.POINTER(CompositeExt), ALLOC_FN,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
+        lib.gsr_forward_ext.restype = ctypes.c_int
+        lib.gsr_backward_ext.argtypes = [ctypes.POINTER(BackwardArgs), ctypes.POINTER(CompositeExt), ALLOC_FN,
+                                         ctypes.c_void_p, ctypes.c_void_p]
+        lib.gsr_backward_ext.restype = ctypes.c_int
     lib.gsr_mark_visible.argtypes = [ctypes.c_int, _fp, _fp, _fp, _fp, ctypes.c_void_p]
     lib.gsr_mark_visible.restype = ctypes.c_int
     lib.gsr_sh_backward_views.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp,

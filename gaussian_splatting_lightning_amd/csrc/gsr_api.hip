@@ -81,12 +81,14 @@ enum Stage {
     ST_BK_SCATTER,
     ST_SEG_SORT,
     ST_ADAM_SH,
+    ST_BACKGROUND_GRAD,
     ST_COUNT
 };
 const char *kStageNames[ST_COUNT] = {"preprocess", "depth_sort", "instance_scan", "readback",
                                      "expand",     "tile_sort",  "tile_ranges",   "render_fwd",
                                      "render_bwd", "big_reduce", "preprocess_bwd", "sh_views",
-                                     "bucket_count", "bucket_scatter", "seg_sort", "adam_sh_views"};
+                                     "bucket_count", "bucket_scatter", "seg_sort", "adam_sh_views",
+                                     "background_grad"};
 
 struct Profiler {
     std::mutex mu;
@@ -359,6 +361,34 @@ int check_common(int P, int D, int M, int W, int H, const float *means3D, const 
     return GSR_OK;
 }
 
+// gsr_composite_ext as the library reads it: the fields the caller's struct_size covers, NULL past it (and all NULL
+// without the struct: gsr_forward / gsr_backward)
+struct CompositeExt {
+    bool given = false;
+    const float *background_image = nullptr;
+    float *out_alpha = nullptr;
+    const float *dL_dalpha = nullptr;
+    float *dL_dbackground = nullptr, *dL_dbackground_image = nullptr;
+};
+int read_composite_ext(const gsr_composite_ext *ext, const float *background, CompositeExt &e) {
+    if (!ext) return GSR_OK;
+    if (ext->struct_size < offsetof(gsr_composite_ext, background_image) + sizeof(ext->background_image))
+        return fail(GSR_ERR_ARG, "gsr_composite_ext: struct_size ends before the first pointer field");
+    gsr_composite_ext full{};
+    memcpy(&full, ext, std::min(ext->struct_size, sizeof(full)));
+    // a field the caller's struct covers only in part is not there
+    auto has = [&](size_t off) { return off + sizeof(void *) <= ext->struct_size; };
+    e.given = true;
+    e.background_image = full.background_image;
+    if (has(offsetof(gsr_composite_ext, out_alpha))) e.out_alpha = full.out_alpha;
+    if (has(offsetof(gsr_composite_ext, dL_dalpha))) e.dL_dalpha = full.dL_dalpha;
+    if (has(offsetof(gsr_composite_ext, dL_dbackground))) e.dL_dbackground = full.dL_dbackground;
+    if (has(offsetof(gsr_composite_ext, dL_dbackground_image))) e.dL_dbackground_image = full.dL_dbackground_image;
+    if (!background && !e.background_image)
+        return fail(GSR_ERR_ARG, "one of background and gsr_composite_ext.background_image is required");
+    return GSR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -422,10 +452,18 @@ void gsr_state_layout_query(int P, int64_t R, int W, int H, gsr_state_layout *ca
 
 int gsr_forward(gsr_forward_args *a, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr,
                 int64_t *num_rendered) {
+    return gsr_forward_ext(a, nullptr, alloc, alloc_ctx, stream_ptr, num_rendered);
+}
+
+int gsr_forward_ext(gsr_forward_args *a, const gsr_composite_ext *ext, gsr_alloc_fn alloc, void *alloc_ctx,
+                    void *stream_ptr, int64_t *num_rendered) {
     if (!a || !alloc || !num_rendered) return fail(GSR_ERR_ARG, "null argument");
-    int rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
-                          a->scales, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
-                          a->background);
+    CompositeExt e;
+    int rc = read_composite_ext(ext, a->background, e);
+    if (rc) return rc;
+    rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
+                      a->scales, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
+                      e.background_image ? e.background_image : a->background);
     if (rc) return rc;
     if (!a->out_color || (a->P > 0 && !a->radii)) return fail(GSR_ERR_ARG, "out_color and radii are required");
     hipStream_t stream = (hipStream_t)stream_ptr;
@@ -437,8 +475,14 @@ int gsr_forward(gsr_forward_args *a, gsr_alloc_fn alloc, void *alloc_ctx, void *
     *num_rendered = 0;
     a->num_big_out = 0;
     if (P == 0) {
-        // the reference returns its zero-initialised outputs untouched when P == 0
-        GSR_HIP(hipMemsetAsync(a->out_color, 0, sizeof(float) * 3 * (size_t)W * H, stream));
+        // the reference returns its zero-initialised outputs untouched when P == 0; with a gsr_composite_ext the
+        // colour is what the composite writes where no Gaussian reaches: the background, alpha 0
+        if (e.given) {
+            launch_background_fill(stream, (size_t)W * H, a->background, e.background_image, a->out_color, e.out_alpha);
+            GSR_HIP(hipGetLastError());
+        } else {
+            GSR_HIP(hipMemsetAsync(a->out_color, 0, sizeof(float) * 3 * (size_t)W * H, stream));
+        }
         if (a->out_invdepth) GSR_HIP(hipMemsetAsync(a->out_invdepth, 0, sizeof(float) * (size_t)W * H, stream));
         return GSR_OK;
     }
@@ -700,7 +744,8 @@ int gsr_forward(gsr_forward_args *a, gsr_alloc_fn alloc, void *alloc_ctx, void *
     rp.point_list = b.point_list; rp.tile_loaded = im.tile_loaded;
     rp.inv = b.inv;
     rp.rec = g.rec;
-    rp.bg = a->background;
+    rp.bg = a->background ? a->background : e.background_image;
+    rp.bg_image = e.background_image; rp.out_alpha = e.out_alpha;
     rp.out_color = a->out_color; rp.out_invdepth = a->out_invdepth; rp.final_T = im.final_T;
     rp.n_contrib = im.n_contrib; rp.tile_last = im.tile_last;
     // checkpoints for the segmented backward ("bwd_seg" 1, spacing "seg_k" instances: 32 or a multiple of 64) while the image
@@ -778,16 +823,46 @@ static int zero_camera_grads(const gsr_backward_args *a, hipStream_t stream) {  
     return GSR_OK;
 }
 
+// The background's gradients (gsr_composite_ext), written with the composite: one pass over final_T (null: no Gaussian,
+// T = 1) and dL_dpix on the caller's stream, its per-workgroup partials in the caller's GSR_BUF_BACKGROUND_PARTIALS
+static int background_grads(const gsr_backward_args *a, const CompositeExt &e, const float *final_T, gsr_alloc_fn alloc,
+                            void *alloc_ctx, hipStream_t stream) {
+    if (!e.dL_dbackground && !e.dL_dbackground_image) return GSR_OK;
+    const size_t HW = (size_t)a->W * a->H;
+    float *partials = nullptr;
+    if (e.dL_dbackground) {
+        partials = reinterpret_cast<float *>(alloc(alloc_ctx, GSR_BUF_BACKGROUND_PARTIALS, background_partials_bytes(HW)));
+        if (!partials) return fail(GSR_ERR_ALLOC, "background partials allocation failed");
+    }
+    GSR_STAGE(ST_BACKGROUND_GRAD, a->debug != 0,
+              launch_background_grad(stream, HW, final_T, a->dL_dpix, e.dL_dbackground_image, e.dL_dbackground, partials));
+    return GSR_OK;
+}
+
 int gsr_backward(const gsr_backward_args *a, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr) {
+    return gsr_backward_ext(a, nullptr, alloc, alloc_ctx, stream_ptr);
+}
+
+int gsr_backward_ext(const gsr_backward_args *a, const gsr_composite_ext *ext, gsr_alloc_fn alloc, void *alloc_ctx,
+                     void *stream_ptr) {
     if (!a || !alloc) return fail(GSR_ERR_ARG, "null argument");
-    int rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
-                          a->scales, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
-                          a->background);
+    CompositeExt e;
+    int rc = read_composite_ext(ext, a->background, e);
     if (rc) return rc;
+    if (a->stages == GSR_BWD_GAUSSIANS)  // the per-Gaussian stage reads no background: only its presence counts
+        e.out_alpha = nullptr, e.dL_dalpha = nullptr, e.dL_dbackground = e.dL_dbackground_image = nullptr;
+    rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
+                      a->scales, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
+                      e.background_image ? e.background_image : a->background);
+    if (rc) return rc;
+    const bool bg_grads = e.dL_dbackground || e.dL_dbackground_image;
+    if (bg_grads && !a->dL_dpix) return fail(GSR_ERR_ARG, "dL_dpix is required for the background gradients");
     if (a->P == 0) {
-        if (!camera_grads(a)) return GSR_OK;
+        if (!camera_grads(a) && !bg_grads) return GSR_OK;
         StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
-        return zero_camera_grads(a, (hipStream_t)stream_ptr);
+        rc = background_grads(a, e, nullptr, alloc, alloc_ctx, (hipStream_t)stream_ptr);  // T_final = 1
+        if (rc) return rc;
+        return camera_grads(a) ? zero_camera_grads(a, (hipStream_t)stream_ptr) : GSR_OK;
     }
     if (!a->dL_dpix || !a->radii) return fail(GSR_ERR_ARG, "dL_dpix and radii are required");
     if (!a->geom_buffer || !a->image_buffer || (a->R > 0 && !a->binning_buffer))
@@ -850,7 +925,8 @@ int gsr_backward(const gsr_backward_args *a, gsr_alloc_fn alloc, void *alloc_ctx
         }
         rp.tile_last = im.tile_last; rp.tile_loaded = im.tile_loaded;
         rp.rec = g.rec;
-        rp.bg = a->background; rp.final_T = im.final_T; rp.dL_dpix = a->dL_dpix; rp.dL_dinvdepth = a->dL_dinvdepth;
+        rp.bg = a->background ? a->background : e.background_image; rp.bg_image = e.background_image; rp.dL_dalpha = e.dL_dalpha;
+        rp.final_T = im.final_T; rp.dL_dpix = a->dL_dpix; rp.dL_dinvdepth = a->dL_dinvdepth;
         rp.rows = rows;
         rp.live = tuning("bwd_live", 1) ? g.live : nullptr;
         rp.live_valid = g.counters + CNT_LIVE_VALID;
@@ -868,6 +944,10 @@ int gsr_backward(const gsr_backward_args *a, gsr_alloc_fn alloc, void *alloc_ctx
         bp.rows = rows; bp.bigsum = bigsum;
         bp.nbig_dev = nbig_on_device ? g.counters + CNT_BIG : nullptr;
         GSR_STAGE(ST_BIG_REDUCE, dbg, launch_big_reduce(stream, bp, nbig));
+    }
+    if (a->stages != GSR_BWD_GAUSSIANS) {  // (with nothing rendered the forward left final_T = 1 everywhere)
+        rc = background_grads(a, e, im.final_T, alloc, alloc_ctx, stream);
+        if (rc) return rc;
     }
     if (a->stages == GSR_BWD_COMPOSITE) return GSR_OK;
     // Chunk-relative outputs (a split backward) address Gaussian g0's row: shift them so the kernel indexes every

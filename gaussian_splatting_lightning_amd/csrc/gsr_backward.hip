@@ -120,7 +120,10 @@ __device__ __forceinline__ void wave_reduce_pair_store(const float r0[8], const 
 // of BWD_BATCH instances: wave 0 stages the records, every wave reduces its own per-instance sums into its
 // s_part plane, and after a barrier wave 0 adds the planes in part order and writes the gradient row.  The
 // per-instance reductions are repeated PARTS times, so it pays only where latency, not issue, is the limit.
-template <bool HAS_INV, int PARTS>
+// EXT (gsr_composite_ext: a background image and / or an alpha gradient given): each pixel's scalar starts from
+// D0 = B(pix) . dL/dpix(pix) - dL/dalpha(pix) instead of bg . dL/dpix; nothing else of the walk knows.  Instantiations
+// of their own (as render_bwd_v5_kernel's), so the plain call runs the code it ran before.
+template <bool HAS_INV, int PARTS, bool EXT = false>
 __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdParams p) {
     constexpr int NP = PIX_PER_LANE / PARTS;
     __shared__ float4 s_a[BWD_BATCH];
@@ -165,7 +168,18 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
         dp1[k] = inside ? p.dL_dpix[HW + pid] : 0.f;
         dp2[k] = inside ? p.dL_dpix[2 * HW + pid] : 0.f;
         dinv[k] = (HAS_INV && inside) ? p.dL_dinvdepth[pid] : 0.f;
-        D[k] = fmaf(bg2, dp2[k], fmaf(bg1, dp1[k], bg0 * dp0[k]));
+        if constexpr (EXT) {  // D0 = B(pix) . dL/dpix(pix) - dL/dalpha(pix) (wave-uniform branches)
+            float b0 = bg0, b1 = bg1, b2 = bg2;
+            if (p.bg_image) {
+                b0 = p.bg_image[pid];
+                b1 = p.bg_image[HW + pid];
+                b2 = p.bg_image[2 * HW + pid];
+            }
+            D[k] = fmaf(b2, dp2[k], fmaf(b1, dp1[k], b0 * dp0[k]));
+            if (p.dL_dalpha) D[k] -= inside ? p.dL_dalpha[pid] : 0.f;
+        } else {
+            D[k] = fmaf(bg2, dp2[k], fmaf(bg1, dp1[k], bg0 * dp0[k]));
+        }
     }
     const float hW = 0.5f * p.W, hH = 0.5f * p.H;
 
@@ -297,7 +311,13 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
 // checkpoint at the segment's end: T = T_e and D = (colour still to come . dL/dpix + T_final bg . dL/dpix) / T_e, the
 // scalar accumulator's value there (D_k T_(k+1) = sum_(j > k) w_j c_j . dL/dpix + T_final bg . dL/dpix).  Without
 // checkpoints every tile is one segment.  Rows agree with the one-walk backward to rounding.
-template <bool HAS_INV, bool UNION = false, bool SEG = false, bool GUARD = false>
+// EXT (gsr_composite_ext: a background image and / or an alpha gradient given): each pixel's scalar starts from
+// D0 = B(pix) . dL/dpix(pix) - dL/dalpha(pix) instead of bg . dL/dpix, in the prologue, by wave-uniform branches; the
+// segment restart below carries any D0, and nothing else of the walk knows.  Instantiations of their own, so the plain
+// call runs the code it ran before: as runtime branches of the one prologue, the wait for the prologue's loads came
+// before the first batch's record loads instead of under them (render_bwd 0.296 -> 0.301 ms at cfg 3), and ahead of the
+// loads with a select the segmented walk of small images still measured 0.5 us slower.
+template <bool HAS_INV, bool UNION = false, bool SEG = false, bool GUARD = false, bool EXT = false>
 __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? GSR_BWD_SEG_MINW : GSR_BWD_MINW) void render_bwd_v5_kernel(RenderBwdParams p) {
     __shared__ FwdRec s_rec[BWD_BATCH];
     __shared__ __attribute__((aligned(16))) float s_part[BWD_BATCH][PART];  // [instance][10 sums]
@@ -377,7 +397,18 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? GSR_BWD_SEG_MINW : GSR_BWD_MI
         dp1[k] = inside ? p.dL_dpix[HW + pid] : 0.f;
         dp2[k] = inside ? p.dL_dpix[2 * HW + pid] : 0.f;
         dinv[k] = (HAS_INV && inside) ? p.dL_dinvdepth[pid] : 0.f;
-        D[k] = fmaf(bg2, dp2[k], fmaf(bg1, dp1[k], bg0 * dp0[k]));
+        if constexpr (EXT) {  // D0 = B(pix) . dL/dpix(pix) - dL/dalpha(pix) (wave-uniform branches)
+            float b0 = bg0, b1 = bg1, b2 = bg2;
+            if (p.bg_image) {
+                b0 = p.bg_image[pid];
+                b1 = p.bg_image[HW + pid];
+                b2 = p.bg_image[2 * HW + pid];
+            }
+            D[k] = fmaf(b2, dp2[k], fmaf(b1, dp1[k], b0 * dp0[k]));
+            if (p.dL_dalpha) D[k] -= inside ? p.dL_dalpha[pid] : 0.f;
+        } else {
+            D[k] = fmaf(bg2, dp2[k], fmaf(bg1, dp1[k], bg0 * dp0[k]));
+        }
         prow[k] = (float)py;  // dy = y - pixel row in one subtraction, as the forward
     }
     if (SEG && !last_seg) {  // start from the checkpoint before instance hi
@@ -611,6 +642,18 @@ __global__ __launch_bounds__(1024) void seg_list_kernel(const uint32_t *__restri
     if (tid == 0) *count = total;
 }
 
+// one composite form, plain or with the gsr_composite_ext start value
+template <bool HAS_INV, bool UNION = false, bool SEG = false, bool GUARD = false>
+static void launch_v5(dim3 grid, dim3 block, hipStream_t s, const RenderBwdParams &q) {
+    if (q.bg_image || q.dL_dalpha) render_bwd_v5_kernel<HAS_INV, UNION, SEG, GUARD, true><<<grid, block, 0, s>>>(q);
+    else render_bwd_v5_kernel<HAS_INV, UNION, SEG, GUARD><<<grid, block, 0, s>>>(q);
+}
+template <bool HAS_INV, int PARTS>
+static void launch_parts(dim3 grid, dim3 block, hipStream_t s, const RenderBwdParams &q) {
+    if (q.bg_image || q.dL_dalpha) render_bwd_parts_kernel<HAS_INV, PARTS, true><<<grid, block, 0, s>>>(q);
+    else render_bwd_parts_kernel<HAS_INV, PARTS><<<grid, block, 0, s>>>(q);
+}
+
 void launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
     if (p.num_tiles <= 0) return;
     RenderBwdParams q = p;
@@ -622,10 +665,10 @@ void launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
         // segmented walk (800x800, 2500 tiles: one wave per 128-instance segment against 4 part-waves per tile)
         seg_list_kernel<<<1, 1024, 0, s>>>(p.tile_order, p.tile_last, p.num_tiles, p.ck_flag, q.seg_list, q.seg_count);
         const dim3 grid((uint32_t)seg_slots((int64_t)p.num_rendered, (uint32_t)p.num_tiles)), block(64);
-        if (gd && p.dL_dinvdepth) render_bwd_v5_kernel<true, false, true, true><<<grid, block, 0, s>>>(q);
-        else if (gd) render_bwd_v5_kernel<false, false, true, true><<<grid, block, 0, s>>>(q);
-        else if (p.dL_dinvdepth) render_bwd_v5_kernel<true, false, true><<<grid, block, 0, s>>>(q);
-        else render_bwd_v5_kernel<false, false, true><<<grid, block, 0, s>>>(q);
+        if (gd && p.dL_dinvdepth) launch_v5<true, false, true, true>(grid, block, s, q);
+        else if (gd) launch_v5<false, false, true, true>(grid, block, s, q);
+        else if (p.dL_dinvdepth) launch_v5<true, false, true>(grid, block, s, q);
+        else launch_v5<false, false, true>(grid, block, s, q);
         return;
     }
     // "bwd_parts" 1, 2 or 4; 0 (default): 4 or 2 while that many part-waves fit within bwd_part_slots
@@ -638,11 +681,11 @@ void launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
     if (parts == 2 || parts == 4) {
         const dim3 grid(p.num_tiles), block(64 * parts);
         if (p.dL_dinvdepth) {
-            if (parts == 2) render_bwd_parts_kernel<true, 2><<<grid, block, 0, s>>>(q);
-            else render_bwd_parts_kernel<true, 4><<<grid, block, 0, s>>>(q);
+            if (parts == 2) launch_parts<true, 2>(grid, block, s, q);
+            else launch_parts<true, 4>(grid, block, s, q);
         } else {
-            if (parts == 2) render_bwd_parts_kernel<false, 2><<<grid, block, 0, s>>>(q);
-            else render_bwd_parts_kernel<false, 4><<<grid, block, 0, s>>>(q);
+            if (parts == 2) launch_parts<false, 2>(grid, block, s, q);
+            else launch_parts<false, 4>(grid, block, s, q);
         }
         return;
     }
@@ -654,18 +697,18 @@ void launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
     const int un = tuning("bwd_union", -1);
     const bool u = un < 0 ? p.num_rendered > (uint64_t)1024 * (uint64_t)p.num_tiles : un != 0;
     if (gd) {
-        if (p.dL_dinvdepth && u) render_bwd_v5_kernel<true, true, false, true><<<grid, block, 0, s>>>(q);
-        else if (p.dL_dinvdepth) render_bwd_v5_kernel<true, false, false, true><<<grid, block, 0, s>>>(q);
-        else if (u) render_bwd_v5_kernel<false, true, false, true><<<grid, block, 0, s>>>(q);
-        else render_bwd_v5_kernel<false, false, false, true><<<grid, block, 0, s>>>(q);
+        if (p.dL_dinvdepth && u) launch_v5<true, true, false, true>(grid, block, s, q);
+        else if (p.dL_dinvdepth) launch_v5<true, false, false, true>(grid, block, s, q);
+        else if (u) launch_v5<false, true, false, true>(grid, block, s, q);
+        else launch_v5<false, false, false, true>(grid, block, s, q);
         return;
     }
     if (p.dL_dinvdepth) {
-        if (u) render_bwd_v5_kernel<true, true><<<grid, block, 0, s>>>(q);
-        else render_bwd_v5_kernel<true><<<grid, block, 0, s>>>(q);
+        if (u) launch_v5<true, true>(grid, block, s, q);
+        else launch_v5<true>(grid, block, s, q);
     } else {
-        if (u) render_bwd_v5_kernel<false, true><<<grid, block, 0, s>>>(q);
-        else render_bwd_v5_kernel<false><<<grid, block, 0, s>>>(q);
+        if (u) launch_v5<false, true>(grid, block, s, q);
+        else launch_v5<false>(grid, block, s, q);
     }
 }
 

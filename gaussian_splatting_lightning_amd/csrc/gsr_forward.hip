@@ -649,7 +649,12 @@ void launch_tile_order(hipStream_t s, const uint2 *ranges, const uint32_t *tile_
 // SMASK (whole tiles): per batch, scalar masks cb[k] collect the instances some pixel of strip k took, and each loaded
 // instance's 4-bit strip mask goes to strip_mask[s] -- the backward then walks exactly the strips that contributed
 // instead of the conservative cell_mask (bitwise the same gradients: a skipped strip has no contributing pixel).
-template <int NPIX, int MIN_WAVES, bool CKPT = false, bool GUARD = false, bool SMASK = false>
+// EXT (gsr_composite_ext: a background image and / or the rendered alpha asked for): the epilogue takes each pixel's
+// background from the (3,H,W) image and stores alpha = 1 - T_final, as wave-uniform branches outside the instance loop.
+// Instantiations of their own, so the plain call runs the code it ran before the struct existed: as runtime branches
+// of the one epilogue the two pointers cost 4 SGPRs across the walk (102 SGPRs took the 6- and 4-wave whole-tile forms
+// from 8 to 7 waves per SIMD) and the 4-part forward of small images measured 1.4 us (2 %) slower.
+template <int NPIX, int MIN_WAVES, bool CKPT = false, bool GUARD = false, bool SMASK = false, bool EXT = false>
 __global__ __launch_bounds__(256, MIN_WAVES) void render_fwd_v6_kernel(RenderFwdParams p) {
     constexpr int PARTS = 4 / NPIX;
     static_assert(!SMASK || PARTS == 1, "strip masks are recorded by whole-tile waves");
@@ -843,9 +848,22 @@ __global__ __launch_bounds__(256, MIN_WAVES) void render_fwd_v6_kernel(RenderFwd
             const float Tk = T[k];
             p.final_T[pid] = Tk;
             p.n_contrib[pid] = last[k];
-            p.out_color[pid] = C0[k] + Tk * bg0;
-            p.out_color[HW + pid] = C1[k] + Tk * bg1;
-            p.out_color[2 * HW + pid] = C2[k] + Tk * bg2;
+            if constexpr (EXT) {  // the same expression on the pixel's own background; the rendered alpha
+                float b0 = bg0, b1 = bg1, b2 = bg2;
+                if (p.bg_image) {  // wave-uniform
+                    b0 = p.bg_image[pid];
+                    b1 = p.bg_image[HW + pid];
+                    b2 = p.bg_image[2 * HW + pid];
+                }
+                p.out_color[pid] = C0[k] + Tk * b0;
+                p.out_color[HW + pid] = C1[k] + Tk * b1;
+                p.out_color[2 * HW + pid] = C2[k] + Tk * b2;
+                if (p.out_alpha) p.out_alpha[pid] = 1.0f - Tk;  // wave-uniform
+            } else {
+                p.out_color[pid] = C0[k] + Tk * bg0;
+                p.out_color[HW + pid] = C1[k] + Tk * bg1;
+                p.out_color[2 * HW + pid] = C2[k] + Tk * bg2;
+            }
             if (p.out_invdepth) p.out_invdepth[pid] = ID[k];
             mx = max(mx, last[k]);
         }
@@ -884,6 +902,14 @@ int render_fwd_parts(int num_tiles) {
     return (parts == 2 || parts == 4) ? parts : 1;
 }
 
+// one composite form, plain or with the gsr_composite_ext epilogue
+template <int NPIX, int MIN_WAVES, bool CKPT = false, bool GUARD = false, bool SMASK = false>
+static void launch_fwd_form(dim3 grid, dim3 block, hipStream_t s, const RenderFwdParams &p) {
+    if (p.bg_image || p.out_alpha)
+        render_fwd_v6_kernel<NPIX, MIN_WAVES, CKPT, GUARD, SMASK, true><<<grid, block, 0, s>>>(p);
+    else render_fwd_v6_kernel<NPIX, MIN_WAVES, CKPT, GUARD, SMASK><<<grid, block, 0, s>>>(p);
+}
+
 void launch_render_fwd(hipStream_t s, const RenderFwdParams &p0) {
     if (p0.num_tiles <= 0) return;
     RenderFwdParams p = p0;
@@ -898,32 +924,32 @@ void launch_render_fwd(hipStream_t s, const RenderFwdParams &p0) {
     const bool sm = parts == 1 && p.strip_mask && tuning("smask", 1);
     if (!sm) p.strip_mask = nullptr;
     if (tuning("guard", 0)) {  // 6 waves per SIMD whole-tile: the guard's double exp needs the registers
-        if (parts == 1 && sm) render_fwd_v6_kernel<4, 6, false, true, true><<<grid, block, 0, s>>>(p);
-        else if (parts == 1) render_fwd_v6_kernel<4, 6, false, true><<<grid, block, 0, s>>>(p);
+        if (parts == 1 && sm) launch_fwd_form<4, 6, false, true, true>(grid, block, s, p);
+        else if (parts == 1) launch_fwd_form<4, 6, false, true>(grid, block, s, p);
         else if (parts == 4 && p.ckpt && p.ctot && p.ck_k >= CK_MIN_K && p.ck_k % 32 == 0 &&
                  (p.ck_k == 32 || p.ck_k % 64 == 0))
-            render_fwd_v6_kernel<1, 8, true, true><<<grid, block, 0, s>>>(p);
-        else if (parts == 2) render_fwd_v6_kernel<2, 8, false, true><<<grid, block, 0, s>>>(p);
-        else render_fwd_v6_kernel<1, 8, false, true><<<grid, block, 0, s>>>(p);
+            launch_fwd_form<1, 8, true, true>(grid, block, s, p);
+        else if (parts == 2) launch_fwd_form<2, 8, false, true>(grid, block, s, p);
+        else launch_fwd_form<1, 8, false, true>(grid, block, s, p);
         return;
     }
     if (parts == 1) {
         // 8 waves per SIMD (64 VGPRs, one 8-byte spill outside the pair loop): cfg3 0.180 -> 0.172 ms, cfg5 0.517 ->
         // 0.478 ms against 6 waves (65 VGPRs, i.e. 7 resident)
         const int mw = tuning("fwd_whole_waves", 8);
-        if (sm) render_fwd_v6_kernel<4, 8, false, false, true><<<grid, block, 0, s>>>(p);
-        else if (mw >= 8) render_fwd_v6_kernel<4, 8><<<grid, block, 0, s>>>(p);
-        else if (mw >= 6) render_fwd_v6_kernel<4, 6><<<grid, block, 0, s>>>(p);
-        else render_fwd_v6_kernel<4, 4><<<grid, block, 0, s>>>(p);
+        if (sm) launch_fwd_form<4, 8, false, false, true>(grid, block, s, p);
+        else if (mw >= 8) launch_fwd_form<4, 8>(grid, block, s, p);
+        else if (mw >= 6) launch_fwd_form<4, 6>(grid, block, s, p);
+        else launch_fwd_form<4, 4>(grid, block, s, p);
         return;
     }
     const int mw = tuning("fwd_part_waves", 8);
     if (parts == 4 && p.ckpt && p.ctot && p.ck_k >= CK_MIN_K && p.ck_k % 32 == 0 && (p.ck_k == 32 || p.ck_k % 64 == 0))
-        render_fwd_v6_kernel<1, 8, true><<<grid, block, 0, s>>>(p);
-    else if (parts == 2 && mw >= 8) render_fwd_v6_kernel<2, 8><<<grid, block, 0, s>>>(p);
-    else if (parts == 2) render_fwd_v6_kernel<2, 4><<<grid, block, 0, s>>>(p);
-    else if (mw >= 8) render_fwd_v6_kernel<1, 8><<<grid, block, 0, s>>>(p);
-    else render_fwd_v6_kernel<1, 4><<<grid, block, 0, s>>>(p);
+        launch_fwd_form<1, 8, true>(grid, block, s, p);
+    else if (parts == 2 && mw >= 8) launch_fwd_form<2, 8>(grid, block, s, p);
+    else if (parts == 2) launch_fwd_form<2, 4>(grid, block, s, p);
+    else if (mw >= 8) launch_fwd_form<1, 8>(grid, block, s, p);
+    else launch_fwd_form<1, 4>(grid, block, s, p);
 }
 
 // ------------------------------------------------------------------------------------------------

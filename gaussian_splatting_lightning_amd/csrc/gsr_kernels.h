@@ -168,6 +168,10 @@ struct RenderFwdParams {
     // which strips took each loaded instance; *smask_valid = 1 if this launch wrote them, else 0
     uint8_t *strip_mask = nullptr;
     uint32_t *smask_valid = nullptr;
+    // gsr_composite_ext: a (3,H,W) background read per pixel in place of bg (bg then points at the image too: it is
+    // still read), and the rendered alpha 1 - final_T (H,W); null: the plain epilogue
+    const float *bg_image = nullptr;
+    float *out_alpha = nullptr;
 };
 void launch_render_fwd(hipStream_t s, const RenderFwdParams &p);
 int render_fwd_parts(int num_tiles);  // row-strip parts per tile launch_render_fwd uses (1: whole tiles)
@@ -209,8 +213,22 @@ struct RenderBwdParams {
     uint4 *zf_ptr[ZF_SEGS] = {};
     uint64_t zf_pre16[ZF_SEGS + 1] = {};  // prefix sums of the segments' lengths
     uint32_t *zf_odd[ZF_ODD] = {};
+    // gsr_composite_ext: the walk's scalar starts from bg_image(pix) . dL_dpix(pix) (in place of bg, which then points
+    // at the image too: it is still read) minus dL_dalpha(pix); null: the plain start
+    const float *bg_image = nullptr, *dL_dalpha = nullptr;
 };
 void launch_render_bwd(hipStream_t s, const RenderBwdParams &p);
+
+// ---- background gradients, empty-scene fill (gsr_background.hip) ----
+// dL/dbackground_image = final_T * dL_dpix (3,H,W) and / or dL/dbackground (3) = its sum over the pixels, in one pass
+// over final_T (null: 1, no Gaussian) and dL_dpix plus the fixed-order sum of the per-workgroup partials
+// (background_partials_bytes(HW) bytes, needed only with dbg).
+size_t background_partials_bytes(size_t HW);
+void launch_background_grad(hipStream_t s, size_t HW, const float *final_T, const float *dL_dpix, float *dimg,
+                            float *dbg, float *partials);
+// the forward of a scene without Gaussians: colour = the background (bg_image (3,H,W), else bg (3)), alpha = 0
+void launch_background_fill(hipStream_t s, size_t HW, const float *bg, const float *bg_image, float *out_color,
+                            float *out_alpha);
 
 struct BigReduceParams {
     const uint32_t *big_list, *inst_start, *tiles;

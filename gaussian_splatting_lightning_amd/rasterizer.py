@@ -11,6 +11,9 @@ The names, argument meaning, return values and error behaviour are those of the 
                                  cov3D_precomp) -> (color (3,H,W), radii (P,) int32, invdepth (1,H,W))
     GaussianRasterizer.markVisible(positions) -> bool (P,)
     rasterize_gaussians(...)        functional form
+Beyond upstream: GaussianRasterizer(settings, return_alpha=True) / rasterize_gaussians(..., return_alpha=True) also
+return alpha (1,H,W) = 1 - final transmittance, and settings.bg may be a (3,H,W) image and receives a gradient where
+it requires grad (gsr_forward_ext / gsr_backward_ext); without either the call is upstream's.
 Every computation runs in the HIP kernels on the tensors' device; the scratch state the backward needs
 (geometry/binning/image buffers) lives in uint8 tensors saved on the autograd context.
 """
@@ -122,8 +125,23 @@ class ForwardState(NamedTuple):
     M: int
 
 
-def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-    """One call of gsr_forward.  Returns (color (3,H,W), radii (P,), invdepth (1,H,W), ForwardState)."""
+def _background(bg, H: int, W: int) -> bool:
+    """Whether a background tensor is a per-pixel (3,H,W) image (True) or the (3,) vector; RuntimeError otherwise."""
+    if bg is not None and tuple(bg.shape) == (3,):
+        return False
+    if bg is not None and tuple(bg.shape) == (3, H, W):
+        return True
+    raise RuntimeError(f"bg must have shape (3,) or (3, {H}, {W}), got {None if bg is None else tuple(bg.shape)}")
+
+
+def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                return_alpha=False):
+    """One call of gsr_forward.  Returns (color (3,H,W), radii (P,), invdepth (1,H,W), ForwardState).
+    raster_settings.bg is the (3,) background or a (3,H,W) image, one background per pixel.  return_alpha=True returns
+    (color, radii, invdepth, alpha (1,H,W), ForwardState), alpha = 1 - the transmittance left behind the pixel's last
+    contributor (0 where no Gaussian reaches).  Either goes through gsr_forward_ext; the plain call is gsr_forward.
+    With P == 0 the two differ in colour: the plain call returns zeros (upstream's early return), the ext call what the
+    composite writes where no Gaussian reaches, the background; every P > 0 colour is bitwise the same in both."""
     lib = _native.load()
     device = means3D.device
     if device.type != "cuda":
@@ -141,6 +159,7 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
     rot_c = _prep(rotations, device, "rotations")
     cov_c = _prep(cov3Ds_precomp, device, "cov3D_precomp")
     bg = _prep(rs.bg, device, "bg")
+    bg_image = _background(bg, H, W)
     view = _prep(rs.viewmatrix, device, "viewmatrix")
     proj = _prep(rs.projmatrix, device, "projmatrix")
     campos = _prep(rs.campos, device, "campos")
@@ -150,9 +169,13 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
     color = torch.empty(3, H, W, dtype=torch.float32, device=device)
     invdepth = torch.empty(1, H, W, dtype=torch.float32, device=device)
     radii = torch.empty(P, dtype=torch.int32, device=device)
+    alpha = torch.empty(1, H, W, dtype=torch.float32, device=device) if return_alpha else None
+    ext = None
+    if bg_image or return_alpha:
+        ext = _native.CompositeExt(background_image=_ptr(bg) if bg_image else None, out_alpha=_ptr(alpha))
     bufs = _Buffers(device)
     a = _native.ForwardArgs(
-        P=P, D=int(rs.sh_degree), M=M, W=W, H=H, background=_ptr(bg), means3D=_ptr(means3D_c),
+        P=P, D=int(rs.sh_degree), M=M, W=W, H=H, background=None if bg_image else _ptr(bg), means3D=_ptr(means3D_c),
         colors_precomp=_ptr(col_c), opacities=_ptr(op_c), scales=_ptr(sc_c),
         scale_modifier=float(rs.scale_modifier), rotations=_ptr(rot_c), cov3D_precomp=_ptr(cov_c),
         viewmatrix=_ptr(view), projmatrix=_ptr(proj), campos=_ptr(campos), tan_fovx=float(rs.tanfovx),
@@ -161,18 +184,34 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
         out_invdepth=invdepth.data_ptr(), radii=radii.data_ptr())
     num_rendered = ctypes.c_int64(0)
     with torch.cuda.device(device):  # the library also switches to its stream's device (gsr_api.hip)
-        rc = lib.gsr_forward(ctypes.byref(a), bufs.callback, None, _stream_handle(device),
-                             ctypes.byref(num_rendered))
+        if ext is None:
+            rc = lib.gsr_forward(ctypes.byref(a), bufs.callback, None, _stream_handle(device),
+                                 ctypes.byref(num_rendered))
+        else:
+            rc = lib.gsr_forward_ext(ctypes.byref(a), ctypes.byref(ext), bufs.callback, None, _stream_handle(device),
+                                     ctypes.byref(num_rendered))
     bufs.raise_pending()
     _native.check(rc, "rasterize_gaussians")
     state = ForwardState(means3D_c, sh_c, col_c, op_c, sc_c, rot_c, cov_c, radii, bg, view, proj, campos,
                          bufs.get(_native.GSR_BUF_GEOM), bufs.get(_native.GSR_BUF_BINNING),
                          bufs.get(_native.GSR_BUF_IMAGE), int(num_rendered.value), int(a.num_big_out), M)
+    if return_alpha:
+        return color, radii, invdepth, alpha, state
     return color, radii, invdepth, state
 
 
+def _alpha_grad(grad_out_alpha, H: int, W: int):
+    """The upstream gradient of alpha as a contiguous float32 (H*W) block, or None."""
+    if grad_out_alpha is None:
+        return None
+    if grad_out_alpha.numel() != H * W:
+        raise RuntimeError(f"grad_out_alpha must have shape (1, {H}, {W}), got {tuple(grad_out_alpha.shape)}")
+    return grad_out_alpha.to(torch.float32).contiguous()
+
+
 def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_depth=None, out=None,
-                 compact_sh=False, accumulate_stats=False, camera_grads=False):
+                 compact_sh=False, accumulate_stats=False, camera_grads=False, grad_out_alpha=None,
+                 background_grad=False):
     """One call of gsr_backward.  Returns a dict of gradients (means3D, means2D, shs, colors_precomp,
     opacities, scales, rotations, cov3D_precomp); entries are None where the input was absent.
     `out` may supply preallocated contiguous float32 destinations (e.g. views into one flat buffer that is
@@ -186,12 +225,17 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     per-view factor that `sh_backward_views` expands after an all-gather (multiview.py).
     camera_grads=True adds the gradients of the camera, as three independent inputs: viewmatrix (4,4) (column 3
     zero), projmatrix (4,4) (column 2 zero) and campos (3) (zero without SH colours); `out` may supply them under
-    those names.  Deterministic sums over the Gaussians; the other gradients are bitwise what they are without."""
+    those names.  Deterministic sums over the Gaussians; the other gradients are bitwise what they are without.
+    grad_out_alpha (1,H,W) or (H,W) is the upstream gradient of forward_raw's alpha.  background_grad=True adds "bg",
+    the gradient of the background the forward composited over, in its shape -- (3,) (a fixed-order sum over the
+    pixels, bitwise reproducible) or (3,H,W); `out` may supply it as out["bg"].  With a (3,H,W) background, an alpha
+    gradient or background_grad the call is gsr_backward_ext; the Gaussians' gradients without an alpha gradient are
+    bitwise those of the plain call."""
     lib = _native.load()
     rs = raster_settings
     st = state
-    device = st.means3D.device
-    P = st.means3D.shape[0]
+    device = st.radii.device  # (a scene without Gaussians keeps no means3D; its background gradients still exist)
+    P = st.radii.shape[0]
     M = st.M
     H, W = int(rs.image_height), int(rs.image_width)
     if grad_out_color is None:
@@ -199,6 +243,8 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     grad_out_color = grad_out_color.to(torch.float32).contiguous()
     if grad_out_depth is not None:
         grad_out_depth = grad_out_depth.to(torch.float32).contiguous()
+    grad_out_alpha = _alpha_grad(grad_out_alpha, H, W)
+    bg_image = _background(st.bg, H, W)
     f32 = dict(dtype=torch.float32, device=device)
     out = out or {}
 
@@ -228,9 +274,16 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     dview = dst("viewmatrix", 4, 4) if camera_grads else None
     dproj = dst("projmatrix", 4, 4) if camera_grads else None
     dcampos = dst("campos", 3) if camera_grads else None
+    dbg = dst("bg", *st.bg.shape) if (background_grad or "bg" in out) else None
+    ext = None
+    if bg_image or grad_out_alpha is not None or dbg is not None:
+        ext = _native.CompositeExt(background_image=_ptr(st.bg) if bg_image else None, dL_dalpha=_ptr(grad_out_alpha),
+                                   dL_dbackground=None if bg_image else _ptr(dbg),
+                                   dL_dbackground_image=_ptr(dbg) if bg_image else None)
     bufs = _Buffers(device)
     a = _native.BackwardArgs(
-        P=P, D=int(rs.sh_degree), M=M, W=W, H=H, R=st.num_rendered, num_big=st.num_big, background=_ptr(st.bg),
+        P=P, D=int(rs.sh_degree), M=M, W=W, H=H, R=st.num_rendered, num_big=st.num_big,
+        background=None if bg_image else _ptr(st.bg),
         means3D=_ptr(st.means3D), colors_precomp=_ptr(st.colors_precomp), opacities=_ptr(st.opacities),
         scales=_ptr(st.scales), scale_modifier=float(rs.scale_modifier), rotations=_ptr(st.rotations),
         cov3D_precomp=_ptr(st.cov3D_precomp), viewmatrix=_ptr(st.viewmatrix), projmatrix=_ptr(st.projmatrix),
@@ -245,23 +298,29 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
         campos_rows=cam_rows, campos_rank=cam_rank, campos_nrows=cam_n,
         dL_dviewmatrix=_ptr(dview), dL_dprojmatrix=_ptr(dproj), dL_dcampos=_ptr(dcampos))
     with torch.cuda.device(device):
-        rc = lib.gsr_backward(ctypes.byref(a), bufs.callback, None, _stream_handle(device))
+        if ext is None:
+            rc = lib.gsr_backward(ctypes.byref(a), bufs.callback, None, _stream_handle(device))
+        else:
+            rc = lib.gsr_backward_ext(ctypes.byref(a), ctypes.byref(ext), bufs.callback, None, _stream_handle(device))
     bufs.raise_pending()
     _native.check(rc, "rasterize_gaussians_backward")
     camera = dict(viewmatrix=dview, projmatrix=dproj, campos=dcampos) if camera_grads else {}
+    if dbg is not None:
+        camera["bg"] = dbg
     return dict(
         **camera,
         means3D=dmeans3D, means2D=dmeans2D,
         shs=dsh.view_as(st.shs) if (st.shs is not None and dsh is not None) else None, colors_sh=dcsh,
         colors_precomp=dcolors if st.colors_precomp is not None else None,
-        colors=dcolors, opacities=dopac.view_as(st.opacities),
+        colors=dcolors, opacities=dopac.view_as(st.opacities) if st.opacities is not None else dopac,
         scales=dscales if st.scales is not None else None,
         rotations=drot if st.rotations is not None else None,
         cov3D_precomp=dcov if st.cov3D_precomp is not None else None, cov3D=dcov)
 
 
 def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_out_depth, chunks, on_chunk=None,
-                     compact_sh=False, accumulate_stats=False, after_composite=None):
+                     compact_sh=False, accumulate_stats=False, after_composite=None, grad_out_alpha=None,
+                     bg_out=None):
     """The backward split so that a gradient exchange overlaps it (multiview.py): ONE gsr_backward call for the
     compositing backward (GSR_BWD_COMPOSITE: instance gradient rows into a scratch buffer kept here), then one call
     per Gaussian chunk for the per-Gaussian stage (GSR_BWD_GAUSSIANS), each followed by on_chunk(k) -- which may
@@ -272,19 +331,41 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
     Results are bitwise those of one backward_raw call: every Gaussian is computed by the same code.
     A chunk's out may also hold viewmatrix (4,4), projmatrix (4,4) and campos (3): the camera gradients summed over
     that chunk's Gaussians (the caller adds the chunks; each chunk needs its own destinations).
-    after_composite(), when given, runs between the compositing call and the first per-Gaussian call."""
+    after_composite(), when given, runs between the compositing call and the first per-Gaussian call.
+    grad_out_alpha: the upstream gradient of alpha, read by the compositing call (as backward_raw's); bg_out: a
+    contiguous float32 destination shaped like the background, which the compositing call fills with its gradient
+    (backward_raw's "bg")."""
     lib = _native.load()
     rs = raster_settings
     st = state
-    device = st.means3D.device
-    P, M = st.means3D.shape[0], st.M
+    device = st.radii.device  # (as backward_raw: a scene without Gaussians keeps no means3D)
+    P, M = st.radii.shape[0], st.M
     H, W = int(rs.image_height), int(rs.image_width)
+    if grad_out_color is None:
+        grad_out_color = torch.zeros(3, H, W, dtype=torch.float32, device=device)
     grad_out_color = grad_out_color.to(torch.float32).contiguous()
     if grad_out_depth is not None:
         grad_out_depth = grad_out_depth.to(torch.float32).contiguous()
+    grad_out_alpha = _alpha_grad(grad_out_alpha, H, W)
+    bg_image = _background(st.bg, H, W)
+    ext = None  # (the per-Gaussian calls take it too: with a background image there is no background vector)
+    if bg_out is not None and (tuple(bg_out.shape) != tuple(st.bg.shape) or bg_out.dtype != torch.float32
+                               or not bg_out.is_contiguous()):
+        raise RuntimeError(f"bg_out must be a contiguous float32 tensor of shape {tuple(st.bg.shape)}")
+    if bg_image or grad_out_alpha is not None or bg_out is not None:
+        ext = _native.CompositeExt(background_image=_ptr(st.bg) if bg_image else None, dL_dalpha=_ptr(grad_out_alpha),
+                                   dL_dbackground=None if bg_image else _ptr(bg_out),
+                                   dL_dbackground_image=_ptr(bg_out) if bg_image else None)
+
+    def call(a):
+        if ext is None:
+            return lib.gsr_backward(ctypes.byref(a), bufs.callback, None, _stream_handle(device))
+        return lib.gsr_backward_ext(ctypes.byref(a), ctypes.byref(ext), bufs.callback, None, _stream_handle(device))
+
     bufs = _Buffers(device)
     base = dict(
-        P=P, D=int(rs.sh_degree), M=M, W=W, H=H, R=st.num_rendered, num_big=st.num_big, background=_ptr(st.bg),
+        P=P, D=int(rs.sh_degree), M=M, W=W, H=H, R=st.num_rendered, num_big=st.num_big,
+        background=None if bg_image else _ptr(st.bg),
         means3D=_ptr(st.means3D), colors_precomp=_ptr(st.colors_precomp), opacities=_ptr(st.opacities),
         scales=_ptr(st.scales), scale_modifier=float(rs.scale_modifier), rotations=_ptr(st.rotations),
         cov3D_precomp=_ptr(st.cov3D_precomp), viewmatrix=_ptr(st.viewmatrix), projmatrix=_ptr(st.projmatrix),
@@ -295,7 +376,7 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
         densify_accumulate=int(bool(accumulate_stats)))
     with torch.cuda.device(device):
         a = _native.BackwardArgs(stages=_native.GSR_BWD_COMPOSITE, **base)
-        rc = lib.gsr_backward(ctypes.byref(a), bufs.callback, None, _stream_handle(device))
+        rc = call(a)
         bufs.raise_pending()
         _native.check(rc, "rasterize_gaussians_backward (composite)")
         scratch = bufs.get(_native.GSR_BUF_BWD_SCRATCH)
@@ -330,7 +411,7 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
                 max_radii2D=_ptr(out.get("max_radii2D")), campos_rows=cam_rows, campos_rank=cam_rank,
                 campos_nrows=cam_n, dL_dviewmatrix=_ptr(out.get("viewmatrix")),
                 dL_dprojmatrix=_ptr(out.get("projmatrix")), dL_dcampos=_ptr(out.get("campos")), **base)
-            rc = lib.gsr_backward(ctypes.byref(a), bufs.callback, None, _stream_handle(device))
+            rc = call(a)
             bufs.raise_pending()
             _native.check(rc, f"rasterize_gaussians_backward (chunk {k})")
             if on_chunk is not None:
@@ -356,29 +437,34 @@ def _campos_rows(spec):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, *camera):
-        # camera: () or the settings' (viewmatrix, projmatrix, campos) once more, as inputs autograd can hand a
-        # gradient to (rasterize_gaussians); the values are read from the settings either way
-        color, radii, invdepth, st = forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations,
-                                                 cov3Ds_precomp, raster_settings)
+                raster_settings, return_alpha=False, bg=None, *camera):
+        # bg: None or the settings' bg once more, camera: () or the settings' (viewmatrix, projmatrix, campos) once
+        # more, as inputs autograd can hand a gradient to (rasterize_gaussians); the values are read from the settings
+        # either way
+        res = forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                          return_alpha=return_alpha)
+        st = res[-1]
         ctx.raster_settings = raster_settings
+        ctx.bg = None if bg is None else (tuple(bg.shape), bg.device)
         ctx.camera = [(tuple(t.shape), t.device) for t in camera]
         ctx.meta = (st.num_rendered, st.num_big, st.M)
         ctx.present = tuple(t is not None for t in st)
         empty = torch.empty(0, device=means3D.device)
         ctx.save_for_backward(*[(t if t is not None else empty) for t in st[:15]])
         ctx.set_materialize_grads(False)
-        return color, radii, invdepth
+        return res[:-1]  # (color, radii, invdepth) or (color, radii, invdepth, alpha)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth):
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, grad_out_alpha=None):
         saved = ctx.saved_tensors
         tensors = [t if present else None for t, present in zip(saved, ctx.present[:15])]
         st = ForwardState(*tensors, *ctx.meta)
         need = ctx.needs_input_grad
-        g = backward_raw(st, ctx.raster_settings, grad_out_color, grad_out_depth, camera_grads=any(need[9:]))
+        g = backward_raw(st, ctx.raster_settings, grad_out_color, grad_out_depth, camera_grads=any(need[11:]),
+                         grad_out_alpha=grad_out_alpha, background_grad=need[10])
         camera = tuple(g[name].reshape(shape).to(dev) if wanted else None for name, (shape, dev), wanted in
-                       zip(("viewmatrix", "projmatrix", "campos"), ctx.camera, need[9:]))
+                       zip(("viewmatrix", "projmatrix", "campos"), ctx.camera, need[11:]))
+        camera = (None, g["bg"].reshape(ctx.bg[0]).to(ctx.bg[1]) if need[10] else None) + camera
         return (g["means3D"] if need[0] else None,
                 g["means2D"] if need[1] else None,
                 g["shs"] if need[2] else None,
@@ -391,17 +477,23 @@ class _RasterizeGaussians(torch.autograd.Function):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
+                        raster_settings, return_alpha=False):
     """Differentiable with respect to the Gaussians' tensors and, where raster_settings.viewmatrix, .projmatrix or
     .campos requires grad, to those three as independent inputs (projmatrix being the full view-projection product:
-    a caller optimising a pose builds projmatrix and campos from its view matrix in torch, which chains the three)."""
+    a caller optimising a pose builds projmatrix and campos from its view matrix in torch, which chains the three).
+    raster_settings.bg -- (3,) or a (3,H,W) image -- receives its gradient too where it requires grad.
+    return_alpha=True returns (color, radii, invdepth, alpha (1,H,W)) with alpha = 1 - the transmittance left behind
+    each pixel's last contributor; alpha takes part in autograd like color and invdepth.  return_alpha (or an image
+    bg) does not change color, except with no Gaussian at all (P == 0): the plain call then returns zeros like
+    upstream, this one the background (forward_raw)."""
     rs = raster_settings
     camera = (rs.viewmatrix, rs.projmatrix, rs.campos)
     if not (torch.is_grad_enabled() and all(torch.is_tensor(t) for t in camera)
             and any(t.requires_grad for t in camera)):
         camera = ()  # the call as it is without camera gradients
+    bg = rs.bg if (torch.is_grad_enabled() and torch.is_tensor(rs.bg) and rs.bg.requires_grad) else None
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, *camera)
+                                     cov3Ds_precomp, raster_settings, bool(return_alpha), bg, *camera)
 
 
 def sh_backward_views(means3D: torch.Tensor, campos: torch.Tensor, dcolors_sh: torch.Tensor, sh_degree: int, M: int,
@@ -449,9 +541,12 @@ def mark_visible(positions: torch.Tensor, viewmatrix: torch.Tensor, projmatrix: 
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings):
+    def __init__(self, raster_settings: GaussianRasterizationSettings, return_alpha: bool = False):
+        """return_alpha=True: the call returns (color, radii, invdepth, alpha (1,H,W)); with P == 0 its color is the
+        background where the plain call's is zero (rasterize_gaussians)."""
         super().__init__()
         self.raster_settings = raster_settings
+        self.return_alpha = bool(return_alpha)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         with torch.no_grad():
@@ -467,4 +562,4 @@ class GaussianRasterizer(nn.Module):
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, rs)
+                                   cov3D_precomp, rs, return_alpha=self.return_alpha)

@@ -42,7 +42,8 @@ enum {
     GSR_BUF_BINNING = 1,
     GSR_BUF_IMAGE = 2,
     GSR_BUF_BWD_SCRATCH = 3,
-    GSR_BUF_CAMERA_PARTIALS = 4 /* gsr_backward, only when a camera gradient is asked for; free after the call */
+    GSR_BUF_CAMERA_PARTIALS = 4, /* gsr_backward, only when a camera gradient is asked for; free after the call */
+    GSR_BUF_BACKGROUND_PARTIALS = 5 /* gsr_backward_ext, only when dL_dbackground is asked for; free after the call */
 };
 
 enum {
@@ -166,6 +167,37 @@ enum { GSR_BWD_ALL = 0, GSR_BWD_COMPOSITE = 1, GSR_BWD_GAUSSIANS = 2 };
 /* Replaces `_C.rasterize_gaussians_backward` (RasterizeGaussiansBackwardCUDA -> Rasterizer::backward).
  * Deterministic: per-tile gradient rows are reduced in fixed order (no float atomics). */
 int gsr_backward(const gsr_backward_args *args, gsr_alloc_fn alloc, void *alloc_ctx, void *stream);
+
+/* Rendered alpha, a per-pixel background and the background's gradients: a side struct of gsr_forward_ext /
+ * gsr_backward_ext, versioned by its own size like gsr_state_layout (fields are only appended; the library reads the
+ * fields past the caller's struct_size as NULL), so gsr_forward_args / gsr_backward_args and GSR_ABI_VERSION stay as
+ * they are.  With T_final the transmittance the forward leaves behind a pixel's last contributor:
+ *   out_alpha = 1 - T_final (0 on a pixel no Gaussian reaches);
+ *   out_color_c = C_c + T_final * background_image_c(pix): args->background's expression with the pixel's own value
+ *     (an image whose every pixel is the vector gives the vector's bits);
+ *   backward: the per-pixel scalar that carries the background through the reverse walk starts from
+ *     sum_c B_c(pix) dL_dpix_c(pix) - dL_dalpha(pix); nothing else of the walk changes;
+ *   dL_dbackground_image_c(pix) = T_final(pix) * dL_dpix_c(pix) (one rounding);
+ *   dL_dbackground_c = the sum of that over the pixels, in a fixed tree whose shape depends only on (W, H): per-workgroup
+ *     partials in the caller's GSR_BUF_BACKGROUND_PARTIALS buffer, then one fixed-order pass (no float atomics, bitwise
+ *     reproducible).
+ * background_image and dL_dalpha are read, and the two gradients written, by GSR_BWD_ALL and GSR_BWD_COMPOSITE;
+ * GSR_BWD_GAUSSIANS ignores the struct.  With P = 0 (or nothing rendered) T_final = 1: alpha 0, colour the background,
+ * the gradients dL_dpix and its sums. */
+typedef struct gsr_composite_ext {
+    size_t struct_size;               /* sizeof as the caller was built; fields past it are read as NULL */
+    const float *background_image;    /* (3,H,W) or NULL; when given it replaces args->background (which may then be NULL) */
+    float *out_alpha;                 /* forward: (H,W), fully written, or NULL */
+    const float *dL_dalpha;           /* backward: (H,W) or NULL */
+    float *dL_dbackground;            /* backward: (3), fully written, or NULL */
+    float *dL_dbackground_image;      /* backward: (3,H,W), fully written, or NULL */
+} gsr_composite_ext;
+/* gsr_forward / gsr_backward are these with ext = NULL.  GSR_ERR_ARG, before any device call or allocation, when
+ * neither args->background nor ext->background_image is given or struct_size ends before the first pointer field. */
+int gsr_forward_ext(gsr_forward_args *args, const gsr_composite_ext *ext, gsr_alloc_fn alloc, void *alloc_ctx,
+                    void *stream, int64_t *num_rendered);
+int gsr_backward_ext(const gsr_backward_args *args, const gsr_composite_ext *ext, gsr_alloc_fn alloc, void *alloc_ctx,
+                     void *stream);
 
 /* Multi-view SH gradient from compact per-view factors (no counterpart in the reference, whose batch size is
  * one view: gs_lightning_module.py:139-141).  dL_dsh[g] = sum_v basis(normalize(means3D[g] - campos[v]))
