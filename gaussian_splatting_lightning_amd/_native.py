@@ -62,6 +62,13 @@ class CompositeExt(ctypes.Structure):  # include/gsrast.h gsr_composite_ext (ver
         super().__init__(struct_size=ctypes.sizeof(CompositeExt), **fields)
 
 
+class AbsgradExt(ctypes.Structure):  # include/gsrast.h gsr_absgrad_ext (versioned by struct_size)
+    _fields_ = [("struct_size", ctypes.c_size_t), ("dL_dmeans2D_abs", _fp), ("densify_abs", ctypes.c_int)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=ctypes.sizeof(AbsgradExt), **fields)
+
+
 class AdamGroup(ctypes.Structure):
     _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("n", ctypes.c_int64),
                 ("lr", ctypes.c_double), ("step", ctypes.c_int64)]
@@ -124,7 +131,7 @@ EXPORTED_SYMBOLS = (
     "gsr_activations_forward", "gsr_activations_backward",
     "gsr_densify_workspace_bytes", "gsr_densify_classify", "gsr_densify_apply", "gsr_ply_unpack", "gsr_ply_pack",
     "gsr_knn_workspace_bytes", "gsr_knn_mean_dist2", "gsr_debug_wave_stamps",
-    "gsr_forward_ext", "gsr_backward_ext",
+    "gsr_forward_ext", "gsr_backward_ext", "gsr_backward_abs", "gsr_bwd_scratch_bytes_abs",
 )
 
 _lib = None
@@ -153,6 +160,12 @@ def load(path: str | None = None):
         lib.gsr_backward_ext.argtypes = [ctypes.POINTER(BackwardArgs), ctypes.POINTER(CompositeExt), ALLOC_FN,
                                          ctypes.c_void_p, ctypes.c_void_p]
         lib.gsr_backward_ext.restype = ctypes.c_int
+    if hasattr(lib, "gsr_backward_abs"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
+        lib.gsr_backward_abs.argtypes = [ctypes.POINTER(BackwardArgs), ctypes.POINTER(CompositeExt),
+                                         ctypes.POINTER(AbsgradExt), ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p]
+        lib.gsr_backward_abs.restype = ctypes.c_int
+        lib.gsr_bwd_scratch_bytes_abs.argtypes = [ctypes.c_int64, ctypes.c_int64]
+        lib.gsr_bwd_scratch_bytes_abs.restype = ctypes.c_size_t
     lib.gsr_mark_visible.argtypes = [ctypes.c_int, _fp, _fp, _fp, _fp, ctypes.c_void_p]
     lib.gsr_mark_visible.restype = ctypes.c_int
     lib.gsr_sh_backward_views.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp,

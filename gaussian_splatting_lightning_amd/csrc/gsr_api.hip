@@ -389,6 +389,21 @@ int read_composite_ext(const gsr_composite_ext *ext, const float *background, Co
     return GSR_OK;
 }
 
+// gsr_absgrad_ext as the library reads it: a field the caller's struct does not cover whole is NULL / 0
+struct AbsgradExt {
+    float *dL_dmeans2D_abs = nullptr;
+    int densify_abs = 0;
+};
+void read_absgrad_ext(const gsr_absgrad_ext *x, AbsgradExt &e) {
+    if (!x) return;
+    gsr_absgrad_ext full{};
+    memcpy(&full, x, std::min(x->struct_size, sizeof(full)));
+    if (offsetof(gsr_absgrad_ext, dL_dmeans2D_abs) + sizeof(full.dL_dmeans2D_abs) <= x->struct_size)
+        e.dL_dmeans2D_abs = full.dL_dmeans2D_abs;
+    if (offsetof(gsr_absgrad_ext, densify_abs) + sizeof(full.densify_abs) <= x->struct_size)
+        e.densify_abs = full.densify_abs;
+}
+
 }  // namespace
 
 extern "C" {
@@ -407,6 +422,7 @@ size_t gsr_image_buffer_bytes(int W, int H) {
     return carve_image(nullptr, W, H, im);
 }
 size_t gsr_bwd_scratch_bytes(int64_t R, int64_t num_big) { return bwd_scratch_bytes(R, num_big); }
+size_t gsr_bwd_scratch_bytes_abs(int64_t R, int64_t num_big) { return bwd_scratch_bytes_abs(R, num_big); }
 
 void gsr_state_layout_query(int P, int64_t R, int W, int H, gsr_state_layout *caller) {
     if (!caller) return;
@@ -778,13 +794,18 @@ int gsr_forward_ext(gsr_forward_args *a, const gsr_composite_ext *ext, gsr_alloc
 // 78 % of the Gaussians have an identically zero gradient (culled, or no pixel took one; tools/zero_grad_census.py):
 // their ~250 B of zeros are stored by the VALU-bound walk instead of the HBM-bound per-Gaussian pass.  False (no
 // plan): a pointer not 4-B aligned, or too many segments / odd words.
-static bool zero_fill_plan(const gsr_backward_args *a, int64_t g0, int64_t g1, RenderBwdParams &rp) {
+static bool zero_fill_plan(const gsr_backward_args *a, float *dL_dmeans2D_abs, int64_t g0, int64_t g1,
+                           RenderBwdParams &rp) {
     const size_t ng = (size_t)(g1 - g0);
     const bool sh_stage = !a->colors_precomp && a->shs && a->M > 0;  // preprocess_bwd writes the SH outputs
     struct Out { float *p; size_t w; };
     const Out outs[] = {{a->dL_dmeans2D, 3}, {a->dL_dcolors, 3}, {a->dL_dopacity, 1}, {a->dL_dmeans3D, 3},
                         {a->dL_dcov3D, 6}, {sh_stage ? a->dL_dsh : nullptr, (size_t)a->M * 3},
-                        {sh_stage ? a->dL_dcolors_sh : nullptr, 3}, {a->dL_dscales, 3}, {a->dL_drotations, 4}};
+                        {sh_stage ? a->dL_dcolors_sh : nullptr, 3}, {a->dL_dscales, 3}, {a->dL_drotations, 4},
+                        {dL_dmeans2D_abs, 2}};
+    static_assert(sizeof(outs) / sizeof(outs[0]) <= (size_t)RenderBwdParams::ZF_SEGS &&
+                      6 * sizeof(outs) / sizeof(outs[0]) <= (size_t)RenderBwdParams::ZF_ODD,
+                  "one segment and up to 3 + 3 odd words per output");
     RenderBwdParams z = rp;
     z.zf_nseg = z.zf_nodd = 0;
     z.zf_total16 = 0;
@@ -845,10 +866,21 @@ int gsr_backward(const gsr_backward_args *a, gsr_alloc_fn alloc, void *alloc_ctx
 
 int gsr_backward_ext(const gsr_backward_args *a, const gsr_composite_ext *ext, gsr_alloc_fn alloc, void *alloc_ctx,
                      void *stream_ptr) {
+    return gsr_backward_abs(a, ext, nullptr, alloc, alloc_ctx, stream_ptr);
+}
+
+int gsr_backward_abs(const gsr_backward_args *a, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
+                     gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr) {
     if (!a || !alloc) return fail(GSR_ERR_ARG, "null argument");
     CompositeExt e;
     int rc = read_composite_ext(ext, a->background, e);
     if (rc) return rc;
+    AbsgradExt ab;
+    read_absgrad_ext(absgrad, ab);
+    if (ab.densify_abs && !a->densify_stats)
+        return fail(GSR_ERR_ARG, "gsr_absgrad_ext.densify_abs needs densify_stats");
+    if (ab.densify_abs && !ab.dL_dmeans2D_abs)
+        return fail(GSR_ERR_ARG, "gsr_absgrad_ext.densify_abs needs dL_dmeans2D_abs");
     if (a->stages == GSR_BWD_GAUSSIANS)  // the per-Gaussian stage reads no background: only its presence counts
         e.out_alpha = nullptr, e.dL_dalpha = nullptr, e.dL_dbackground = e.dL_dbackground_image = nullptr;
     rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
@@ -899,12 +931,20 @@ int gsr_backward_ext(const gsr_backward_args *a, const gsr_composite_ext *ext, g
     const bool nbig_on_device = a->num_big < 0;
     const uint32_t nbig = nbig_on_device ? R / (BIG_GAUSSIAN_TILES + 1) + 1 : (uint32_t)a->num_big;
     char *scratch = a->stages == GSR_BWD_GAUSSIANS ? a->bwd_scratch
-                                                   : alloc(alloc_ctx, GSR_BUF_BWD_SCRATCH, bwd_scratch_bytes(R, nbig));
+                                                   : alloc(alloc_ctx, GSR_BUF_BWD_SCRATCH,
+                                                           ab.dL_dmeans2D_abs ? bwd_scratch_bytes_abs(R, nbig)
+                                                                              : bwd_scratch_bytes(R, nbig));
     if (!scratch && a->stages != GSR_BWD_GAUSSIANS) return fail(GSR_ERR_ALLOC, "backward scratch allocation failed");
     float *rows = reinterpret_cast<float *>(scratch);
     // Gaussian-major gradient rows: render_bwd scatters its 40-B rows to the instances' expansion indices so
     // the per-Gaussian gather in preprocess_bwd reads each Gaussian's rows contiguously.
     float *bigsum = bwd_bigsum_ptr(scratch, R);
+    // the 8-B abs rows and their big-Gaussian sums, behind them (only with gsr_absgrad_ext.dL_dmeans2D_abs)
+    float2 *abs_rows = nullptr, *bigsum_abs = nullptr;
+    if (ab.dL_dmeans2D_abs && scratch) {
+        abs_rows = reinterpret_cast<float2 *>(bwd_abs_rows_ptr(scratch, R, nbig));
+        bigsum_abs = reinterpret_cast<float2 *>(bwd_abs_bigsum_ptr(scratch, R, nbig));
+    }
 
     bool prezero = false;  // the composite zero-fills the per-Gaussian outputs (zero_fill_plan)
     if (R > 0 && a->stages != GSR_BWD_GAUSSIANS) {
@@ -928,6 +968,7 @@ int gsr_backward_ext(const gsr_backward_args *a, const gsr_composite_ext *ext, g
         rp.bg = a->background ? a->background : e.background_image; rp.bg_image = e.background_image; rp.dL_dalpha = e.dL_dalpha;
         rp.final_T = im.final_T; rp.dL_dpix = a->dL_dpix; rp.dL_dinvdepth = a->dL_dinvdepth;
         rp.rows = rows;
+        rp.abs_rows = abs_rows;
         rp.live = tuning("bwd_live", 1) ? g.live : nullptr;
         rp.live_valid = g.counters + CNT_LIVE_VALID;
         rp.sorted_u = b.sorted_u;
@@ -936,12 +977,13 @@ int gsr_backward_ext(const gsr_backward_args *a, const gsr_composite_ext *ext, g
             rp.ckpt = b.ckpt; rp.ctot = im.ctot; rp.ck_flag = im.ck_flag;
             rp.seg_list = b.seg_list; rp.seg_count = im.seg_count;
         }
-        if (a->stages == GSR_BWD_ALL && tuning("bwd_prezero", 1)) prezero = zero_fill_plan(a, g0, g1, rp);
+        if (a->stages == GSR_BWD_ALL && tuning("bwd_prezero", 1)) prezero = zero_fill_plan(a, ab.dL_dmeans2D_abs, g0, g1, rp);
         GSR_STAGE(ST_RENDER_BWD, dbg, launch_render_bwd(stream, rp));
         BigReduceParams bp;
         bp.big_list = g.big_list; bp.inst_start = g.inst_start; bp.tiles = g.tiles;
         bp.inv = b.inv;
         bp.rows = rows; bp.bigsum = bigsum;
+        bp.abs_rows = abs_rows; bp.bigsum_abs = bigsum_abs;
         bp.nbig_dev = nbig_on_device ? g.counters + CNT_BIG : nullptr;
         GSR_STAGE(ST_BIG_REDUCE, dbg, launch_big_reduce(stream, bp, nbig));
     }
@@ -980,7 +1022,7 @@ int gsr_backward_ext(const gsr_backward_args *a, const gsr_composite_ext *ext, g
     pp.dL_dopacity = rel(a->dL_dopacity, 1); pp.dL_dmeans3D = rel(a->dL_dmeans3D, 3);
     pp.dL_dcov3D = rel(a->dL_dcov3D, 6); pp.dL_dsh = rel(a->dL_dsh, (int64_t)a->M * 3);
     pp.dL_dcolors_sh = rel(a->dL_dcolors_sh, 3);
-    pp.densify_stats = rel(a->densify_stats, 2);
+    pp.densify_stats = ab.densify_abs ? nullptr : rel(a->densify_stats, 2);  // (densify_abs: written by the abs gather)
     pp.densify_accumulate = a->densify_accumulate;
     pp.max_radii2D = rel(a->max_radii2D, 1);
     pp.dL_dscales = rel(a->dL_dscales, 3); pp.dL_drot = rel(a->dL_drotations, 4);
@@ -996,9 +1038,21 @@ int gsr_backward_ext(const gsr_backward_args *a, const gsr_composite_ext *ext, g
         pp.cam_partials = reinterpret_cast<float *>(alloc(alloc_ctx, GSR_BUF_CAMERA_PARTIALS, camera_partials_bytes((int64_t)ng)));
         if (!pp.cam_partials) return fail(GSR_ERR_ALLOC, "camera partials allocation failed");
     }
+    AbsGatherParams gp{};
+    if (ab.dL_dmeans2D_abs) {
+        gp.g0 = (int)g0; gp.g1 = (int)g1;
+        gp.radii = a->radii; gp.tiles = g.tiles; gp.inst_start = g.inst_start; gp.big_slot = g.big_slot; gp.inv = b.inv;
+        gp.live = pp.live; gp.live_valid = pp.live_valid;
+        gp.abs_rows = abs_rows; gp.bigsum_abs = bigsum_abs;
+        gp.out = rel(ab.dL_dmeans2D_abs, 2);
+        gp.densify_stats = ab.densify_abs ? rel(a->densify_stats, 2) : nullptr;
+        gp.densify_accumulate = a->densify_accumulate;
+        gp.prezeroed = prezero ? 1 : 0;
+    }
     GSR_STAGE(ST_PREPROCESS_BWD, dbg, {
         launch_preprocess_bwd(stream, pp);
         if (pp.cam_partials) launch_camera_reduce(stream, pp, a->dL_dviewmatrix, a->dL_dprojmatrix, a->dL_dcampos);
+        if (ab.dL_dmeans2D_abs) launch_abs_gather(stream, gp);
     });
     return GSR_OK;
 }

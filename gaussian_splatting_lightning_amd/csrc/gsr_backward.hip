@@ -60,6 +60,7 @@ constexpr int BWD_BATCH = 32;
 constexpr int PART = 12;  // floats per instance in the LDS partial buffer (10 sums + 2 pad)
 
 __device__ constexpr float kZero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+__device__ constexpr float kZero10[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 // Two instances: the bit-5 exchange pairs each raw sum of instance 0 with the same sum of instance 1 (7 swaps, not
 // the 10 of two moment sets), so every register then holds one quantity (instance b5's) and the moments are formed
@@ -69,13 +70,17 @@ __device__ constexpr float kZero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 // (S, Sx, Sy, Sxx, Sxy, Syy, w0..w3) of instance b5 (the next PART-float row for instance 1).
 // BOTH = false reduces instance 0 alone through the same operation tree (r1 all zero, only its row stored), so an
 // instance's gradient bits do not depend on whether it was paired.
-template <bool BOTH = true>
-__device__ __forceinline__ void wave_reduce_pair_store(const float r0[8], const float r1[8], float *__restrict__ dst,
+// ABS (the absolute screen-space sums asked for): r0 / r1 carry two more raw sums, [8] and [9], the lane's
+// sum |q| |lx| and sum |q| |ly| (pass()); they ride the tree as values 10 and 11.  The bit-3 level then exchanges
+// bb[4] / bb[5] like the pairs before them, so values 8 + 2 b3 + b4 fill the row's two pad floats as well; the lanes
+// with b3 = 0 add the same two operands as the plain form's row_ror:8 of bb[4], so values 0-9 keep their bits.
+template <bool BOTH = true, bool ABS = false>
+__device__ __forceinline__ void wave_reduce_pair_store(const float *r0, const float *r1, float *__restrict__ dst,
                                                        int lane, float *__restrict__ dst1 = nullptr) {
     const bool hi5 = (lane & 32) != 0;
     const float dx = hi5 ? r1[7] : r0[7];
     const float s0 = sum_swap32(r0[0], r1[0]), s1 = sum_swap32(r0[1], r1[1]), s2 = sum_swap32(r0[2], r1[2]);
-    float R[10];
+    float R[ABS ? 12 : 10];
     R[0] = s0;
     R[1] = s0 * dx;
     R[2] = s1;
@@ -84,9 +89,14 @@ __device__ __forceinline__ void wave_reduce_pair_store(const float r0[8], const 
     R[5] = s2;
 #pragma unroll
     for (int i = 0; i < 4; i++) R[6 + i] = sum_swap32(r0[3 + i], r1[3 + i]);
-    float bb[5];
+    if constexpr (ABS) {
+        R[10] = sum_swap32(r0[8], r1[8]);
+        R[11] = sum_swap32(r0[9], r1[9]);
+    }
+    constexpr int NB = ABS ? 6 : 5;
+    float bb[NB];
 #pragma unroll
-    for (int k = 0; k < 5; k++) bb[k] = sum_swap16(R[2 * k], R[2 * k + 1]);
+    for (int k = 0; k < NB; k++) bb[k] = sum_swap16(R[2 * k], R[2 * k + 1]);
     const bool hi3 = (lane & 8) != 0;
     float c[3];
 #pragma unroll
@@ -94,7 +104,12 @@ __device__ __forceinline__ void wave_reduce_pair_store(const float r0[8], const 
         const float keep = hi3 ? bb[2 * m + 1] : bb[2 * m], send = hi3 ? bb[2 * m] : bb[2 * m + 1];
         c[m] = dpp_xadd<0x128>(keep, send);
     }
-    c[2] = dpp_add<0x128>(bb[4]);  // row_ror:8 (= lane ^ 8)
+    if constexpr (ABS) {
+        const float keep = hi3 ? bb[5] : bb[4], send = hi3 ? bb[4] : bb[5];
+        c[2] = dpp_xadd<0x128>(keep, send);
+    } else {
+        c[2] = dpp_add<0x128>(bb[4]);  // row_ror:8 (= lane ^ 8)
+    }
 #pragma unroll
     for (int m = 0; m < 3; m++) {
         c[m] = dpp_add<0xB1>(c[m]);   // quad_perm [1,0,3,2]
@@ -110,8 +125,19 @@ __device__ __forceinline__ void wave_reduce_pair_store(const float r0[8], const 
     if ((lane & 7) == 0) {
         row[low] = c[0];
         row[4 + low] = c[1];
+        if constexpr (ABS) row[8 + low] = c[2];
     }
-    if ((lane & 15) == 0) row[8 + (low & 1)] = c[2];
+    if constexpr (!ABS)
+        if ((lane & 15) == 0) row[8 + (low & 1)] = c[2];
+}
+
+// ABS: the uniform factors of the two absolute sums, applied once per instance after the reduction.  A pixel adds
+// m = -o (W/2, H/2) q (a dx + b dy, b dx + c dy) to dL/dmeans2D; with the staged conic (A, B, C) = -log2(e) (a/2, b, c/2)
+// the lanes summed |q| |2 A dx + B dy| and |q| |B dx + 2 C dy|, so |m| sums to |o| (W/2, H/2) / log2(e) times those.
+constexpr float INV_LOG2E = 0.69314718055994531f;
+__device__ __forceinline__ float2 abs_row(float o, float hW, float hH, float ux, float uy) {
+    const float f = fabsf(o) * INV_LOG2E;
+    return make_float2((f * hW) * ux, (f * hH) * uy);
 }
 
 // Parts variant for small images: PARTS waves of one workgroup share one tile, wave w compositing the lane's
@@ -123,9 +149,11 @@ __device__ __forceinline__ void wave_reduce_pair_store(const float r0[8], const 
 // EXT (gsr_composite_ext: a background image and / or an alpha gradient given): each pixel's scalar starts from
 // D0 = B(pix) . dL/dpix(pix) - dL/dalpha(pix) instead of bg . dL/dpix; nothing else of the walk knows.  Instantiations
 // of their own (as render_bwd_v5_kernel's), so the plain call runs the code it ran before.
-template <bool HAS_INV, int PARTS, bool EXT = false>
+// ABS (RenderBwdParams::abs_rows given): the two absolute sums as well, as in render_bwd_v5_kernel.
+template <bool HAS_INV, int PARTS, bool EXT = false, bool ABS = false>
 __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdParams p) {
     constexpr int NP = PIX_PER_LANE / PARTS;
+    constexpr int NM = ABS ? 10 : 8, NV = ABS ? 12 : 10;  // raw sums (+ dx) per lane, reduced values per instance
     __shared__ float4 s_a[BWD_BATCH];
     __shared__ float4 s_b[BWD_BATCH];
     __shared__ float2 s_c[BWD_BATCH];
@@ -147,6 +175,7 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
     for (uint32_t s = range.x + tl + threadIdx.x; s < range.x + loaded; s += 64 * PARTS) {
         const float z[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         store_row(p.rows, p.sorted_u[s], z);
+        if constexpr (ABS) p.abs_rows[p.sorted_u[s]] = make_float2(0.f, 0.f);
     }
     if (tl == 0) return;  // workgroup-uniform
 
@@ -205,13 +234,19 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
         uint64_t sk[NP];
 #pragma unroll
         for (int k = 0; k < NP; k++) sk[k] = __ballot((mm >> (kbase + k)) & 1u);
-        auto pass = [&](const int j, float m[8]) -> bool {
+        auto pass = [&](const int j, float *m) -> bool {
             const uint32_t idx = (uint32_t)(bend - 1 - j);
             const float4 a = s_a[j], b = s_b[j];  // a: x, y, A, B; b: C, o, r, g
             const float2 c = s_c[j];              // b, 1/depth
             const float dx = a.x - pfx;
             const float P0 = (a.z * dx) * dx, L = a.w * dx;
             float Q0 = 0.f, Q1 = 0.f, Q2 = 0.f, w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
+            // ABS: lx = 2 A dx + B dy and ly = B dx + 2 C dy, one fma each per pixel
+            [[maybe_unused]] float A2 = 0.f, C2 = 0.f, ax = 0.f, ay = 0.f;
+            if constexpr (ABS) {
+                A2 = 2.f * (a.z * dx);
+                C2 = 2.f * b.x;
+            }
             bool any = false;
 #pragma unroll
             for (int k = 0; k < NP; k++) {
@@ -237,6 +272,10 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
                 Q0 += q;
                 Q1 += qdy;
                 Q2 = fmaf(qdy, dy, Q2);
+                if constexpr (ABS) {  // |q lx| = |q| |lx|: one fma with both source modifiers
+                    ax = fmaf(fabsf(q), fabsf(fmaf(a.w, dy, A2)), ax);
+                    ay = fmaf(fabsf(q), fabsf(fmaf(C2, dy, L)), ay);
+                }
             }
             m[0] = Q0;
             m[1] = Q1;
@@ -246,36 +285,40 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
             m[5] = w2;
             m[6] = w3;
             m[7] = dx;
+            if constexpr (ABS) {
+                m[8] = ax;
+                m[9] = ay;
+            }
             return any;
         };
         for (int j = 0; j < cnt; j += 2) {
-            float m0[8];
+            float m0[NM];
             const bool any0 = pass(j, m0);
             float *dst = s_part[w][j];
             if (j + 1 < cnt) {
-                float m1[8];
+                float m1[NM];
                 const bool any1 = pass(j + 1, m1);
                 if (__ballot(any0 || any1)) {
-                    wave_reduce_pair_store(m0, m1, dst, lane);
-                } else if (lane < 10) {
+                    wave_reduce_pair_store<true, ABS>(m0, m1, dst, lane);
+                } else if (lane < NV) {
                     dst[lane] = 0.f;
                     dst[PART + lane] = 0.f;
                 }
             } else if (__ballot(any0)) {
-                wave_reduce_pair_store<false>(m0, kZero8, dst, lane);
-            } else if (lane < 10) {
+                wave_reduce_pair_store<false, ABS>(m0, ABS ? kZero10 : kZero8, dst, lane);
+            } else if (lane < NV) {
                 dst[lane] = 0.f;
             }
         }
         __syncthreads();
         if (w == 0 && lane < cnt) {
-            float u[10];
+            float u[NV];
 #pragma unroll
-            for (int v = 0; v < 10; v++) u[v] = s_part[0][lane][v];
+            for (int v = 0; v < NV; v++) u[v] = s_part[0][lane][v];
 #pragma unroll
             for (int q = 1; q < PARTS; q++)
 #pragma unroll
-                for (int v = 0; v < 10; v++) u[v] += s_part[q][lane][v];
+                for (int v = 0; v < NV; v++) u[v] += s_part[q][lane][v];
             const float o = my_b.y, ca = my_a.z, cb = my_a.w, cc = my_b.x;
             float row[10];
             row[0] = -o * hW * (ca * u[1] + cb * u[2]);
@@ -289,7 +332,13 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
             row[8] = u[8];
             row[9] = u[9];
             store_row(p.rows, my_row, row);
-            if (p.live && row_nonzero(row)) p.live[my_gid] = 1;
+            if constexpr (ABS) {  // (the ten signed sums can cancel to zero where these do not)
+                const float2 ab = abs_row(o, hW, hH, u[10], u[11]);
+                p.abs_rows[my_row] = ab;
+                if (p.live && (row_nonzero(row) || ab.x != 0.f || ab.y != 0.f)) p.live[my_gid] = 1;
+            } else {
+                if (p.live && row_nonzero(row)) p.live[my_gid] = 1;
+            }
         }
         __syncthreads();  // the next batch overwrites the staged records and the sums
     }
@@ -306,6 +355,9 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
 #ifndef GSR_BWD_SEG_MINW
 #define GSR_BWD_SEG_MINW 6  // the segment walk's extra scalars took it to 83 VGPRs (5 waves / SIMD); 6 caps it at 80
 #endif
+#ifndef GSR_BWD_SEG_ABS_MINW
+#define GSR_BWD_SEG_ABS_MINW 5  // the segment walk with the absolute sums spills 1-6 VGPRs under the cap of 80: its own bound
+#endif
 // SEG (small images): the launch slot is a (tile, segment) work item of seg_list; with the forward's checkpoints
 // (*ck_flag = K) segment s walks instances [s K, min((s + 1) K, tile_last)) back to front, starting each pixel from the
 // checkpoint at the segment's end: T = T_e and D = (colour still to come . dL/dpix + T_final bg . dL/dpix) / T_e, the
@@ -317,8 +369,14 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
 // call runs the code it ran before: as runtime branches of the one prologue, the wait for the prologue's loads came
 // before the first batch's record loads instead of under them (render_bwd 0.296 -> 0.301 ms at cfg 3), and ahead of the
 // loads with a select the segmented walk of small images still measured 0.5 us slower.
-template <bool HAS_INV, bool UNION = false, bool SEG = false, bool GUARD = false, bool EXT = false>
-__global__ __launch_bounds__(64, GUARD ? 4 : SEG ? GSR_BWD_SEG_MINW : GSR_BWD_MINW) void render_bwd_v5_kernel(RenderBwdParams p) {
+// ABS (RenderBwdParams::abs_rows given): the absolute screen-space sums (AbsGS) as well.  Per contributing pixel two
+// fma form the linear terms lx, ly of the 2D-mean gradient and two more add |q| |lx|, |q| |ly| to two more lane
+// accumulators; the pair reduction carries 12 values instead of 10 (the LDS row's two pad floats), and lane j stores
+// the instance's 8-B abs row next to its 40-B row.  Instantiations of their own: a call without abs_rows launches
+// the kernels it launched before.
+template <bool HAS_INV, bool UNION = false, bool SEG = false, bool GUARD = false, bool EXT = false, bool ABS = false>
+__global__ __launch_bounds__(64, GUARD ? 4 : SEG ? (ABS ? GSR_BWD_SEG_ABS_MINW : GSR_BWD_SEG_MINW) : GSR_BWD_MINW) void render_bwd_v5_kernel(RenderBwdParams p) {
+    constexpr int NM = ABS ? 10 : 8, NV = ABS ? 12 : 10;  // raw sums (+ dx) per lane, reduced values per instance
     __shared__ FwdRec s_rec[BWD_BATCH];
     __shared__ __attribute__((aligned(16))) float s_part[BWD_BATCH][PART];  // [instance][10 sums]
     // zeros the union walk's per-instance accumulators are loaded from (pass() below); one pair per batch slot, so the
@@ -375,6 +433,7 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? GSR_BWD_SEG_MINW : GSR_BWD_MI
         for (uint32_t s = r0 + tl + lane; s < r0 + loaded; s += 64) {
             const float z[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
             store_row(p.rows, p.sorted_u[s], z);
+            if constexpr (ABS) p.abs_rows[p.sorted_u[s]] = make_float2(0.f, 0.f);
         }
     if (hi == 0) {
         stamp_store(p.stamps, slot, t_start, lane);
@@ -456,7 +515,7 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? GSR_BWD_SEG_MINW : GSR_BWD_MI
         wave_lds_sync();
         // one instance's pass over the lane's pixels: updates T / D, returns the lane's raw sums (Q0, Q1, Q2, w0..w3) and dx in m and the
         // ballot of the lanes that contributed
-        auto pass = [&](const int j, float m[8]) -> uint64_t {
+        auto pass = [&](const int j, float *m) -> uint64_t {
             const uint32_t idx = (uint32_t)(bend - 1 - j);
             const FwdRec &r = s_rec[j];
             const float4 a = r.a, b = r.b;  // a: x, y, A, B; b: C, o, r, g
@@ -472,6 +531,12 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? GSR_BWD_SEG_MINW : GSR_BWD_MI
                 z1 = s_zero[j][1];
             }
             float Q0 = z0.x, Q1 = z0.y, Q2 = z0.z, w0 = z0.w, w1 = z1.x, w2 = z1.y, w3 = z1.z;
+            // ABS: lx = 2 A dx + B dy and ly = B dx + 2 C dy, one fma each per pixel
+            [[maybe_unused]] float A2 = 0.f, C2 = 0.f, ax = 0.f, ay = 0.f;
+            if constexpr (ABS) {
+                A2 = 2.f * (a.z * dx);
+                C2 = 2.f * b.x;
+            }
             uint64_t any = 0;
 #pragma unroll
             for (int k = 0; k < PIX_PER_LANE; k++) {
@@ -510,6 +575,10 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? GSR_BWD_SEG_MINW : GSR_BWD_MI
                 Q0 += q;
                 Q1 += qdy;
                 Q2 = fmaf(qdy, dy, Q2);
+                if constexpr (ABS) {  // |q lx| = |q| |lx|: one fma with both source modifiers
+                    ax = fmaf(fabsf(q), fabsf(fmaf(a.w, dy, A2)), ax);
+                    ay = fmaf(fabsf(q), fabsf(fmaf(C2, dy, L)), ay);
+                }
             }
             m[0] = Q0;
             m[1] = Q1;
@@ -519,6 +588,10 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? GSR_BWD_SEG_MINW : GSR_BWD_MI
             m[5] = w2;
             m[6] = w3;
             m[7] = dx;
+            if constexpr (ABS) {
+                m[8] = ax;
+                m[9] = ay;
+            }
             return any;
         };
         if constexpr (UNION) {
@@ -532,49 +605,50 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? GSR_BWD_SEG_MINW : GSR_BWD_MI
             float4 *z = reinterpret_cast<float4 *>(s_part[lane]);
             z[0] = make_float4(0.f, 0.f, 0.f, 0.f);
             z[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-            *reinterpret_cast<float2 *>(s_part[lane] + 8) = make_float2(0.f, 0.f);
+            if constexpr (ABS) z[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+            else *reinterpret_cast<float2 *>(s_part[lane] + 8) = make_float2(0.f, 0.f);
         }
         while (un) {
             const int j0 = (int)__builtin_ctzll(un);
             un &= ~(1ull << j0);  // s_andn2 with the strip tests' bit (un & (un - 1) costs three SALU)
-            float m0[8];
+            float m0[NM];
             const uint64_t any0 = pass(j0, m0);
             float *dst = s_part[j0];
             if (un) {
                 const int j1 = (int)__builtin_ctzll(un);
                 un &= ~(1ull << j1);
-                float m1[8];
+                float m1[NM];
                 const uint64_t any1 = pass(j1, m1);
                 float *dst1 = s_part[j1];
                 if (any0 | any1) {
-                    wave_reduce_pair_store(m0, m1, dst, lane, dst1);
-                } else if (lane < 10) {
+                    wave_reduce_pair_store<true, ABS>(m0, m1, dst, lane, dst1);
+                } else if (lane < NV) {
                     dst[lane] = 0.f;
                     dst1[lane] = 0.f;
                 }
             } else if (any0) {
-                wave_reduce_pair_store<false>(m0, kZero8, dst, lane);
-            } else if (lane < 10) {
+                wave_reduce_pair_store<false, ABS>(m0, ABS ? kZero10 : kZero8, dst, lane);
+            } else if (lane < NV) {
                 dst[lane] = 0.f;
             }
         }
         } else {
         for (int j = 0; j < cnt; j += 2) {
-            float m0[8];
+            float m0[NM];
             const uint64_t any0 = pass(j, m0);
             float *dst = s_part[j];
             if (j + 1 < cnt) {
-                float m1[8];
+                float m1[NM];
                 const uint64_t any1 = pass(j + 1, m1);
                 if (any0 | any1) {
-                    wave_reduce_pair_store(m0, m1, dst, lane);
-                } else if (lane < 10) {
+                    wave_reduce_pair_store<true, ABS>(m0, m1, dst, lane);
+                } else if (lane < NV) {
                     dst[lane] = 0.f;
                     dst[PART + lane] = 0.f;
                 }
             } else if (any0) {
-                wave_reduce_pair_store<false>(m0, kZero8, dst, lane);
-            } else if (lane < 10) {
+                wave_reduce_pair_store<false, ABS>(m0, ABS ? kZero10 : kZero8, dst, lane);
+            } else if (lane < NV) {
                 dst[lane] = 0.f;
             }
         }
@@ -598,7 +672,14 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? GSR_BWD_SEG_MINW : GSR_BWD_MI
             row[8] = u2.x;
             row[9] = u2.y;
             store_row(p.rows, my_row, row);
-            if (p.live && row_nonzero(row)) p.live[my_gid] = 1;
+            if constexpr (ABS) {  // (the ten signed sums can cancel to zero where these do not)
+                const float2 u3 = *reinterpret_cast<const float2 *>(s_part[lane] + 10);
+                const float2 ab = abs_row(o, hW, hH, u3.x, u3.y);
+                p.abs_rows[my_row] = ab;
+                if (p.live && (row_nonzero(row) || ab.x != 0.f || ab.y != 0.f)) p.live[my_gid] = 1;
+            } else {
+                if (p.live && row_nonzero(row)) p.live[my_gid] = 1;
+            }
         }
         wave_lds_sync();
     }
@@ -645,12 +726,24 @@ __global__ __launch_bounds__(1024) void seg_list_kernel(const uint32_t *__restri
 // one composite form, plain or with the gsr_composite_ext start value
 template <bool HAS_INV, bool UNION = false, bool SEG = false, bool GUARD = false>
 static void launch_v5(dim3 grid, dim3 block, hipStream_t s, const RenderBwdParams &q) {
-    if (q.bg_image || q.dL_dalpha) render_bwd_v5_kernel<HAS_INV, UNION, SEG, GUARD, true><<<grid, block, 0, s>>>(q);
+    const bool ext = q.bg_image || q.dL_dalpha;
+    if (q.abs_rows) {  // the forms with the absolute sums
+        if (ext) render_bwd_v5_kernel<HAS_INV, UNION, SEG, GUARD, true, true><<<grid, block, 0, s>>>(q);
+        else render_bwd_v5_kernel<HAS_INV, UNION, SEG, GUARD, false, true><<<grid, block, 0, s>>>(q);
+        return;
+    }
+    if (ext) render_bwd_v5_kernel<HAS_INV, UNION, SEG, GUARD, true><<<grid, block, 0, s>>>(q);
     else render_bwd_v5_kernel<HAS_INV, UNION, SEG, GUARD><<<grid, block, 0, s>>>(q);
 }
 template <bool HAS_INV, int PARTS>
 static void launch_parts(dim3 grid, dim3 block, hipStream_t s, const RenderBwdParams &q) {
-    if (q.bg_image || q.dL_dalpha) render_bwd_parts_kernel<HAS_INV, PARTS, true><<<grid, block, 0, s>>>(q);
+    const bool ext = q.bg_image || q.dL_dalpha;
+    if (q.abs_rows) {  // the forms with the absolute sums
+        if (ext) render_bwd_parts_kernel<HAS_INV, PARTS, true, true><<<grid, block, 0, s>>>(q);
+        else render_bwd_parts_kernel<HAS_INV, PARTS, false, true><<<grid, block, 0, s>>>(q);
+        return;
+    }
+    if (ext) render_bwd_parts_kernel<HAS_INV, PARTS, true><<<grid, block, 0, s>>>(q);
     else render_bwd_parts_kernel<HAS_INV, PARTS><<<grid, block, 0, s>>>(q);
 }
 
@@ -716,9 +809,11 @@ void launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
 // Gaussians with many instances: one block sums all their rows (fixed stride order, deterministic)
 // into bigsum[slot], which the preprocess backward then reads instead of walking the rows.
 // ------------------------------------------------------------------------------------------------
-template <bool PERSIST>
+// ABS (BigReduceParams::abs_rows given): the 8-B abs rows of the same instances as well, in the same k order and the
+// same tree, into bigsum_abs[slot]; instantiations of their own.
+template <bool PERSIST, bool ABS = false>
 __global__ __launch_bounds__(256) void big_reduce_kernel(BigReduceParams p) {
-    __shared__ float s_part[4][10];
+    __shared__ float s_part[4][ABS ? 12 : 10];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // PERSIST: the big-Gaussian count is only known on the device, so the launch is sized by min(upper bound, 2048)
     // workgroups that loop to it, instead of one per possible big Gaussian; else one workgroup per big Gaussian (no loop:
@@ -728,6 +823,7 @@ __global__ __launch_bounds__(256) void big_reduce_kernel(BigReduceParams p) {
         const uint32_t gidx = p.big_list[bi];
         const uint32_t start = p.inst_start[gidx], cnt = p.tiles[gidx];
         float acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        [[maybe_unused]] float acc_ax = 0.f, acc_ay = 0.f;
         // rows by expansion index (every cell of a big Gaussian's rect is an instance): BR_UNROLL inv words per thread
         // (INV_NONE: the forward composite did not load the instance, no row) are loaded together, then the rows of
         // the loaded instances (most instances of a big Gaussian sit in saturated tiles and have none), summed in the
@@ -735,6 +831,7 @@ __global__ __launch_bounds__(256) void big_reduce_kernel(BigReduceParams p) {
         constexpr int BR_UNROLL = 4;
         for (uint32_t k0 = threadIdx.x; k0 < cnt; k0 += 256 * BR_UNROLL) {
             float r[BR_UNROLL][10];
+            [[maybe_unused]] float2 ra[BR_UNROLL];
             bool use[BR_UNROLL];
             // (guarded loads: unconditional clamped inv loads measured +10 us at cfg 5, where most of the 4 x 256 slots
             // of a big Gaussian lie past its count)
@@ -746,12 +843,19 @@ __global__ __launch_bounds__(256) void big_reduce_kernel(BigReduceParams p) {
             // (rows stay under `if (use)`: loading row 0 for the unwritten ones instead measured slower at cfg 5)
 #pragma unroll
             for (int q = 0; q < BR_UNROLL; q++)
-                if (use[q]) load_row(p.rows, start + k0 + 256 * q, r[q]);
+                if (use[q]) {
+                    load_row(p.rows, start + k0 + 256 * q, r[q]);
+                    if constexpr (ABS) ra[q] = p.abs_rows[start + k0 + 256 * q];
+                }
 #pragma unroll
             for (int q = 0; q < BR_UNROLL; q++)
                 if (use[q]) {
 #pragma unroll
                     for (int v = 0; v < 10; v++) acc[v] += r[q][v];
+                    if constexpr (ABS) {
+                        acc_ax += ra[q].x;
+                        acc_ay += ra[q].y;
+                    }
                 }
         }
 #pragma unroll
@@ -759,12 +863,22 @@ __global__ __launch_bounds__(256) void big_reduce_kernel(BigReduceParams p) {
             const float sum = wave_sum(acc[v]);
             if (lane == 0) s_part[w][v] = sum;
         }
+        if constexpr (ABS) {
+            const float sx = wave_sum(acc_ax), sy = wave_sum(acc_ay);
+            if (lane == 0) {
+                s_part[w][10] = sx;
+                s_part[w][11] = sy;
+            }
+        }
         __syncthreads();
         if (threadIdx.x == 0) {
             float tot[10];
 #pragma unroll
             for (int v = 0; v < 10; v++) tot[v] = ((s_part[0][v] + s_part[1][v]) + s_part[2][v]) + s_part[3][v];
             store_row(p.bigsum, bi, tot);
+            if constexpr (ABS)
+                p.bigsum_abs[bi] = make_float2(((s_part[0][10] + s_part[1][10]) + s_part[2][10]) + s_part[3][10],
+                                               ((s_part[0][11] + s_part[1][11]) + s_part[2][11]) + s_part[3][11]);
         }
         if (!PERSIST) break;
         __syncthreads();  // s_part is rewritten by the next big Gaussian
@@ -773,6 +887,11 @@ __global__ __launch_bounds__(256) void big_reduce_kernel(BigReduceParams p) {
 
 void launch_big_reduce(hipStream_t s, const BigReduceParams &p, uint32_t nbig) {
     if (nbig == 0) return;
+    if (p.abs_rows) {
+        if (p.nbig_dev) big_reduce_kernel<true, true><<<std::min(nbig, 2048u), 256, 0, s>>>(p);
+        else big_reduce_kernel<false, true><<<nbig, 256, 0, s>>>(p);
+        return;
+    }
     if (p.nbig_dev) big_reduce_kernel<true><<<std::min(nbig, 2048u), 256, 0, s>>>(p);
     else big_reduce_kernel<false><<<nbig, 256, 0, s>>>(p);
 }

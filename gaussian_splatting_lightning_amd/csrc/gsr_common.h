@@ -350,6 +350,15 @@ inline size_t bwd_scratch_bytes(int64_t R, int64_t nbig) {
     return align_up((size_t)(R ? R : 1) * GRAD_ROW * sizeof(float), 256) +
            align_up((size_t)(nbig ? nbig : 1) * GRAD_ROW * sizeof(float), 256) + 256;
 }
+// with the absolute screen-space sums: behind that layout (unchanged), one 8-B row per instance, then one per big Gaussian
+inline size_t bwd_scratch_bytes_abs(int64_t R, int64_t nbig) {
+    return bwd_scratch_bytes(R, nbig) + align_up((size_t)(R ? R : 1) * 2 * sizeof(float), 256) +
+           align_up((size_t)(nbig ? nbig : 1) * 2 * sizeof(float), 256);
+}
+inline char *bwd_abs_rows_ptr(char *scratch, int64_t R, int64_t nbig) { return scratch + bwd_scratch_bytes(R, nbig); }
+inline char *bwd_abs_bigsum_ptr(char *scratch, int64_t R, int64_t nbig) {
+    return bwd_abs_rows_ptr(scratch, R, nbig) + align_up((size_t)(R ? R : 1) * 2 * sizeof(float), 256);
+}
 inline float *bwd_bigsum_ptr(char *scratch, int64_t R) {
     return reinterpret_cast<float *>(scratch + align_up((size_t)(R ? R : 1) * GRAD_ROW * sizeof(float), 256));
 }

@@ -216,6 +216,9 @@ struct RenderBwdParams {
     // gsr_composite_ext: the walk's scalar starts from bg_image(pix) . dL_dpix(pix) (in place of bg, which then points
     // at the image too: it is still read) minus dL_dalpha(pix); null: the plain start
     const float *bg_image = nullptr, *dL_dalpha = nullptr;
+    // absolute screen-space sums (gsr_absgrad_ext): R x 8-B rows (sum |m_x|, sum |m_y| of the instance's pixels) by
+    // expansion index like `rows`, or null: the kernels without them
+    float2 *abs_rows = nullptr;
 };
 void launch_render_bwd(hipStream_t s, const RenderBwdParams &p);
 
@@ -236,6 +239,9 @@ struct BigReduceParams {
     const float *rows;
     float *bigsum;  // nbig x GRAD_ROW
     const uint32_t *nbig_dev;  // or null: the launch's nbig is exact; else an upper bound and this the count
+    // the instances' abs rows and their per-big-Gaussian sums (nbig x 8 B), or null: the kernels without them
+    const float2 *abs_rows = nullptr;
+    float2 *bigsum_abs = nullptr;
 };
 void launch_big_reduce(hipStream_t s, const BigReduceParams &p, uint32_t nbig);
 
@@ -268,6 +274,22 @@ struct PreprocessBwdParams {
     float *cam_partials = nullptr;
 };
 void launch_preprocess_bwd(hipStream_t s, const PreprocessBwdParams &p);
+// dL_dmeans2D_abs (P,2) over Gaussians [g0, g1): the Gaussian's abs rows summed in the order, and under the same inv /
+// big-Gaussian / live tests, as launch_preprocess_bwd sums its 40-B rows.  abs_stats: densify_stats (which the
+// per-Gaussian kernel is then not given) is written here, [i][0] from the absolute sums.
+struct AbsGatherParams {
+    int g0, g1;
+    const int *radii;
+    const uint32_t *tiles, *inst_start, *big_slot, *inv;
+    const uint8_t *live;
+    const uint32_t *live_valid;
+    const float2 *abs_rows, *bigsum_abs;
+    float *out;            // (P,2), indexed by the absolute Gaussian index
+    float *densify_stats;  // (P,2) or null (abs_stats)
+    int densify_accumulate;
+    int prezeroed;  // out was zero-filled by the composite: only non-zero rows are stored
+};
+void launch_abs_gather(hipStream_t s, const AbsGatherParams &p);
 // dL/dviewmatrix (16), dL/dprojmatrix (16), dL/dcampos (3) over Gaussians [g0, g1), each fully written or null: the
 // fixed-order sum of the partials launch_preprocess_bwd left in p.cam_partials (g1 > g0)
 size_t camera_partials_bytes(int64_t n);

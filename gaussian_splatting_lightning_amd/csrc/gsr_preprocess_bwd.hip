@@ -695,4 +695,63 @@ void launch_preprocess_bwd(hipStream_t s, const PreprocessBwdParams &p) {
     else launch_preprocess_bwd_t<false>(s, p, grid);
 }
 
+// Absolute screen-space sums (gsr_absgrad_ext), a kernel of its own beside preprocess_bwd_kernel so that none of that
+// kernel's forms changes: one thread per Gaussian adds its 8-B abs rows in expansion order (four inv words, then four
+// rows, in flight together), a big Gaussian takes big_reduce's sum, one without a live flag or a positive radius stays
+// zero -- the tests, and so the order of the additions, of the 40-B gather.  The statistic's norm is formed without
+// contraction (two products, one sum, one square root, each rounded once), so a host can reproduce its bits.
+__device__ __forceinline__ float abs_norm(float x, float y) {
+#pragma clang fp contract(off)
+    const float xx = x * x, yy = y * y;
+    return sqrtf(xx + yy);  // (correctly rounded: the compiler's default for HIP)
+}
+__global__ __launch_bounds__(256) void abs_gather_kernel(AbsGatherParams p) {
+    const int i = p.g0 + blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.g1) return;
+    const int radius = p.radii[i];
+    const bool vis = radius > 0;
+    float2 st_old = make_float2(0.f, 0.f);
+    if (p.densify_stats && p.densify_accumulate) st_old = *reinterpret_cast<const float2 *>(p.densify_stats + 2 * i);
+    float ax = 0.f, ay = 0.f;
+    if (vis && (!p.live || !*p.live_valid || p.live[i])) {
+        const uint32_t start = p.inst_start[i], cnt = p.tiles[i];
+        if (cnt > BIG_GAUSSIAN_TILES) {
+            const float2 v = p.bigsum_abs[p.big_slot[i]];
+            ax = v.x;
+            ay = v.y;
+        } else {
+            for (uint32_t k0 = 0; k0 < cnt; k0 += 4) {
+                uint32_t iv[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) iv[j] = p.inv[start + min(k0 + j, cnt - 1)];  // unconditional (clamped)
+                float2 rw[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const bool use = k0 + j < cnt && iv[j] != INV_NONE;
+                    rw[j] = use ? p.abs_rows[start + k0 + j] : make_float2(0.f, 0.f);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    ax += rw[j].x;
+                    ay += rw[j].y;
+                }
+            }
+        }
+    }
+    if (!p.prezeroed || ax != 0.f || ay != 0.f) {  // (two 4-B stores: the output need only be 4-B aligned)
+        p.out[2 * i] = ax;
+        p.out[2 * i + 1] = ay;
+    }
+    if (p.densify_stats) {
+        float2 st = make_float2(abs_norm(ax, ay), vis ? 1.f : 0.f);
+        if (p.densify_accumulate) st = make_float2(st_old.x + st.x, st_old.y + st.y);
+        *reinterpret_cast<float2 *>(p.densify_stats + 2 * i) = st;
+    }
+}
+
+void launch_abs_gather(hipStream_t s, const AbsGatherParams &p) {
+    if (p.g1 <= p.g0) return;
+    abs_gather_kernel<<<div_up((uint32_t)(p.g1 - p.g0), 256), 256, 0, s>>>(p);
+}
+
 }  // namespace gsr

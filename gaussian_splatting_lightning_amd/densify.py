@@ -41,8 +41,16 @@ def update_max_radii2D(gaussians, radii: torch.Tensor, visible_mask: torch.Tenso
 
 
 @torch.no_grad()
-def update_xyz_gradient(gaussians, screenspace_gradient: torch.Tensor, visible_mask: torch.Tensor) -> None:
-    """gaussian_model.py:178-181."""
+def update_xyz_gradient(gaussians, screenspace_gradient: torch.Tensor, visible_mask: torch.Tensor,
+                        absgrad: torch.Tensor = None) -> None:
+    """gaussian_model.py:178-181.  absgrad, when given (means2D.absgrad of a rasterizer built with absgrad=True, or
+    backward_raw's "means2D_abs"; (P,2) or (P,3)), is accumulated in place of screenspace_gradient: the AbsGS
+    criterion, under which a large Gaussian whose per-pixel gradients cancel is still split.  Its norm is never below
+    the signed one (4-6x above it on this repository's test scenes), and the reference's densify_grad_threshold is not
+    retuned here: a caller that switches it on clones and splits more at the same threshold, and is expected to raise
+    the threshold (AbsGS and gsplat use about twice the signed default)."""
+    if absgrad is not None:
+        screenspace_gradient = absgrad
     gaussians.xyz_grad_accum[visible_mask] += torch.norm(screenspace_gradient[visible_mask, :2], dim=1)
     gaussians.xyz_grad_count[visible_mask] += 1
 

@@ -120,8 +120,11 @@ class GaussianModel(nn.Module):
     def update_max_radii2D(self, radii: torch.Tensor, visible_mask: torch.Tensor) -> None:
         _densify.update_max_radii2D(self, radii, visible_mask)
 
-    def update_xyz_gradient(self, screenspace_gradient: torch.Tensor, visible_mask: torch.Tensor) -> None:
-        _densify.update_xyz_gradient(self, screenspace_gradient, visible_mask)
+    def update_xyz_gradient(self, screenspace_gradient: torch.Tensor, visible_mask: torch.Tensor,
+                            absgrad: Optional[torch.Tensor] = None) -> None:
+        """absgrad: means2D.absgrad of a rasterizer built with absgrad=True, accumulated in place of the signed
+        gradient (densify.update_xyz_gradient; the thresholds are the caller's to retune)."""
+        _densify.update_xyz_gradient(self, screenspace_gradient, visible_mask, absgrad=absgrad)
 
     def densify_and_prune(self, densify_grad_threshold: float, clone_size_threshold: float,
                           prune_opacity_threshold: float, prune_size_threshold: float,

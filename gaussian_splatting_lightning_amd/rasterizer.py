@@ -14,6 +14,8 @@ The names, argument meaning, return values and error behaviour are those of the 
 Beyond upstream: GaussianRasterizer(settings, return_alpha=True) / rasterize_gaussians(..., return_alpha=True) also
 return alpha (1,H,W) = 1 - final transmittance, and settings.bg may be a (3,H,W) image and receives a gradient where
 it requires grad (gsr_forward_ext / gsr_backward_ext); without either the call is upstream's.
+GaussianRasterizer(settings, absgrad=True) / rasterize_gaussians(..., absgrad=True) set means2D.absgrad (P,3) in the
+backward, as gsplat does: the absolute screen-space gradient of AbsGS for densification (gsr_backward_abs).
 Every computation runs in the HIP kernels on the tensors' device; the scratch state the backward needs
 (geometry/binning/image buffers) lives in uint8 tensors saved on the autograd context.
 """
@@ -211,7 +213,7 @@ def _alpha_grad(grad_out_alpha, H: int, W: int):
 
 def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_depth=None, out=None,
                  compact_sh=False, accumulate_stats=False, camera_grads=False, grad_out_alpha=None,
-                 background_grad=False):
+                 background_grad=False, absgrad=False, abs_stats=False):
     """One call of gsr_backward.  Returns a dict of gradients (means3D, means2D, shs, colors_precomp,
     opacities, scales, rotations, cov3D_precomp); entries are None where the input was absent.
     `out` may supply preallocated contiguous float32 destinations (e.g. views into one flat buffer that is
@@ -230,7 +232,16 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     the gradient of the background the forward composited over, in its shape -- (3,) (a fixed-order sum over the
     pixels, bitwise reproducible) or (3,H,W); `out` may supply it as out["bg"].  With a (3,H,W) background, an alpha
     gradient or background_grad the call is gsr_backward_ext; the Gaussians' gradients without an alpha gradient are
-    bitwise those of the plain call."""
+    bitwise those of the plain call.
+    absgrad=True adds "means2D_abs" (P,2): per Gaussian the sum over its pixels of |what the pixel adds to
+    means2D[:, :2]|, the AbsGS densification criterion (gsplat's absgrad), in means2D's units and under every upstream
+    gradient of the call; exactly zero for a Gaussian that is culled or that no pixel takes, deterministic, and every
+    other gradient keeps its bits.  `out` may supply it as out["means2D_abs"] (which also asks for it).
+    abs_stats=True (needs out["densify_stats"]; implies absgrad) forms densify_stats[:, 0] from that vector,
+    sqrt(x * x + y * y) with every operation rounded once, instead of from the signed gradient.  The call is then
+    gsr_backward_abs."""
+    if abs_stats and "densify_stats" not in (out or {}):
+        raise RuntimeError("abs_stats=True needs out['densify_stats']")
     lib = _native.load()
     rs = raster_settings
     st = state
@@ -265,6 +276,7 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     dsh = None if compact_sh else dst("shs", P, max(M, 0), 3)
     dcsh = dst("colors_sh", P, 3) if (compact_sh or "colors_sh" in out) else None
     dstats = dst("densify_stats", P, 2) if "densify_stats" in out else None
+    dabs = dst("means2D_abs", P, 2) if (absgrad or abs_stats or "means2D_abs" in out) else None
     mrad = out.get("max_radii2D")
     if mrad is not None and (tuple(mrad.shape) != (P,) or mrad.dtype != torch.int32 or not mrad.is_contiguous()):
         raise RuntimeError(f"out['max_radii2D'] must be a contiguous int32 tensor of shape ({P},)")
@@ -298,7 +310,12 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
         campos_rows=cam_rows, campos_rank=cam_rank, campos_nrows=cam_n,
         dL_dviewmatrix=_ptr(dview), dL_dprojmatrix=_ptr(dproj), dL_dcampos=_ptr(dcampos))
     with torch.cuda.device(device):
-        if ext is None:
+        if dabs is not None:
+            # (P == 0: the pointer of an empty tensor is passed as NULL and the library writes nothing)
+            ab = _native.AbsgradExt(dL_dmeans2D_abs=_ptr(dabs), densify_abs=int(bool(abs_stats) and P > 0))
+            rc = lib.gsr_backward_abs(ctypes.byref(a), None if ext is None else ctypes.byref(ext), ctypes.byref(ab),
+                                      bufs.callback, None, _stream_handle(device))
+        elif ext is None:
             rc = lib.gsr_backward(ctypes.byref(a), bufs.callback, None, _stream_handle(device))
         else:
             rc = lib.gsr_backward_ext(ctypes.byref(a), ctypes.byref(ext), bufs.callback, None, _stream_handle(device))
@@ -307,6 +324,8 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     camera = dict(viewmatrix=dview, projmatrix=dproj, campos=dcampos) if camera_grads else {}
     if dbg is not None:
         camera["bg"] = dbg
+    if dabs is not None:
+        camera["means2D_abs"] = dabs
     return dict(
         **camera,
         means3D=dmeans3D, means2D=dmeans2D,
@@ -320,7 +339,7 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
 
 def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_out_depth, chunks, on_chunk=None,
                      compact_sh=False, accumulate_stats=False, after_composite=None, grad_out_alpha=None,
-                     bg_out=None):
+                     bg_out=None, abs_stats=False):
     """The backward split so that a gradient exchange overlaps it (multiview.py): ONE gsr_backward call for the
     compositing backward (GSR_BWD_COMPOSITE: instance gradient rows into a scratch buffer kept here), then one call
     per Gaussian chunk for the per-Gaussian stage (GSR_BWD_GAUSSIANS), each followed by on_chunk(k) -- which may
@@ -334,7 +353,10 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
     after_composite(), when given, runs between the compositing call and the first per-Gaussian call.
     grad_out_alpha: the upstream gradient of alpha, read by the compositing call (as backward_raw's); bg_out: a
     contiguous float32 destination shaped like the background, which the compositing call fills with its gradient
-    (backward_raw's "bg")."""
+    (backward_raw's "bg").
+    A chunk's out may hold means2D_abs ((g_end - g_begin), 2), backward_raw's "means2D_abs" for those Gaussians: then
+    every chunk must, since the compositing call produces the rows they are summed from.  abs_stats=True forms each
+    chunk's densify_stats[:, 0] from it (every chunk then needs both)."""
     lib = _native.load()
     rs = raster_settings
     st = state
@@ -357,7 +379,17 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
                                    dL_dbackground=None if bg_image else _ptr(bg_out),
                                    dL_dbackground_image=_ptr(bg_out) if bg_image else None)
 
-    def call(a):
+    chunks = list(chunks)
+    with_abs = [("means2D_abs" in out) for _, _, out in chunks]
+    if any(with_abs) and not all(with_abs):
+        raise RuntimeError("means2D_abs must be in every chunk's out or in none")
+    if abs_stats and not (chunks and all(with_abs) and all("densify_stats" in out for _, _, out in chunks)):
+        raise RuntimeError("abs_stats=True needs out['means2D_abs'] and out['densify_stats'] in every chunk")
+
+    def call(a, ab=None):
+        if ab is not None:
+            return lib.gsr_backward_abs(ctypes.byref(a), None if ext is None else ctypes.byref(ext), ctypes.byref(ab),
+                                        bufs.callback, None, _stream_handle(device))
         if ext is None:
             return lib.gsr_backward(ctypes.byref(a), bufs.callback, None, _stream_handle(device))
         return lib.gsr_backward_ext(ctypes.byref(a), ctypes.byref(ext), bufs.callback, None, _stream_handle(device))
@@ -376,14 +408,17 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
         densify_accumulate=int(bool(accumulate_stats)))
     with torch.cuda.device(device):
         a = _native.BackwardArgs(stages=_native.GSR_BWD_COMPOSITE, **base)
-        rc = call(a)
+        # (the compositing call does not write through the pointer: non-NULL asks for the abs rows)
+        want_abs = any(with_abs) and any(out["means2D_abs"].numel() for _, _, out in chunks)
+        rc = call(a, _native.AbsgradExt(dL_dmeans2D_abs=next(
+            _ptr(out["means2D_abs"]) for _, _, out in chunks if out["means2D_abs"].numel())) if want_abs else None)
         bufs.raise_pending()
         _native.check(rc, "rasterize_gaussians_backward (composite)")
         scratch = bufs.get(_native.GSR_BUF_BWD_SCRATCH)
         if after_composite is not None:
             after_composite()
         widths = dict(means2D=3, colors=3, opacities=1, means3D=3, cov3D=6, shs=3 * max(M, 0), scales=3, rotations=4,
-                      colors_sh=3, densify_stats=2)
+                      colors_sh=3, densify_stats=2, means2D_abs=2)
         for k, (g0, g1, out) in enumerate(chunks):
             n = int(g1) - int(g0)
             cam_rows, cam_rank, cam_n = _campos_rows(out.get("campos_rows"))
@@ -411,7 +446,11 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
                 max_radii2D=_ptr(out.get("max_radii2D")), campos_rows=cam_rows, campos_rank=cam_rank,
                 campos_nrows=cam_n, dL_dviewmatrix=_ptr(out.get("viewmatrix")),
                 dL_dprojmatrix=_ptr(out.get("projmatrix")), dL_dcampos=_ptr(out.get("campos")), **base)
-            rc = call(a)
+            ab = None
+            if want_abs:
+                ab = _native.AbsgradExt(dL_dmeans2D_abs=_ptr(out["means2D_abs"]),
+                                        densify_abs=int(bool(abs_stats) and n > 0))
+            rc = call(a, ab)
             bufs.raise_pending()
             _native.check(rc, f"rasterize_gaussians_backward (chunk {k})")
             if on_chunk is not None:
@@ -437,7 +476,7 @@ def _campos_rows(spec):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, return_alpha=False, bg=None, *camera):
+                raster_settings, return_alpha=False, absgrad=False, bg=None, *camera):
         # bg: None or the settings' bg once more, camera: () or the settings' (viewmatrix, projmatrix, campos) once
         # more, as inputs autograd can hand a gradient to (rasterize_gaussians); the values are read from the settings
         # either way
@@ -445,6 +484,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                           return_alpha=return_alpha)
         st = res[-1]
         ctx.raster_settings = raster_settings
+        # absgrad: the backward sets means2D.absgrad on the caller's tensor (as gsplat's does)
+        ctx.absgrad_of = means2D if (absgrad and torch.is_tensor(means2D)) else None
         ctx.bg = None if bg is None else (tuple(bg.shape), bg.device)
         ctx.camera = [(tuple(t.shape), t.device) for t in camera]
         ctx.meta = (st.num_rendered, st.num_big, st.M)
@@ -460,11 +501,14 @@ class _RasterizeGaussians(torch.autograd.Function):
         tensors = [t if present else None for t, present in zip(saved, ctx.present[:15])]
         st = ForwardState(*tensors, *ctx.meta)
         need = ctx.needs_input_grad
-        g = backward_raw(st, ctx.raster_settings, grad_out_color, grad_out_depth, camera_grads=any(need[11:]),
-                         grad_out_alpha=grad_out_alpha, background_grad=need[10])
+        g = backward_raw(st, ctx.raster_settings, grad_out_color, grad_out_depth, camera_grads=any(need[12:]),
+                         grad_out_alpha=grad_out_alpha, background_grad=need[11], absgrad=ctx.absgrad_of is not None)
+        if ctx.absgrad_of is not None:  # (P,3) with z = 0, so code that takes [:, :2] of means2D.grad works on it
+            m2a = g["means2D_abs"]
+            ctx.absgrad_of.absgrad = torch.cat([m2a, m2a.new_zeros(m2a.shape[0], 1)], dim=1)
         camera = tuple(g[name].reshape(shape).to(dev) if wanted else None for name, (shape, dev), wanted in
-                       zip(("viewmatrix", "projmatrix", "campos"), ctx.camera, need[11:]))
-        camera = (None, g["bg"].reshape(ctx.bg[0]).to(ctx.bg[1]) if need[10] else None) + camera
+                       zip(("viewmatrix", "projmatrix", "campos"), ctx.camera, need[12:]))
+        camera = (None, None, g["bg"].reshape(ctx.bg[0]).to(ctx.bg[1]) if need[11] else None) + camera
         return (g["means3D"] if need[0] else None,
                 g["means2D"] if need[1] else None,
                 g["shs"] if need[2] else None,
@@ -477,7 +521,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, return_alpha=False):
+                        raster_settings, return_alpha=False, absgrad=False):
     """Differentiable with respect to the Gaussians' tensors and, where raster_settings.viewmatrix, .projmatrix or
     .campos requires grad, to those three as independent inputs (projmatrix being the full view-projection product:
     a caller optimising a pose builds projmatrix and campos from its view matrix in torch, which chains the three).
@@ -485,7 +529,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     return_alpha=True returns (color, radii, invdepth, alpha (1,H,W)) with alpha = 1 - the transmittance left behind
     each pixel's last contributor; alpha takes part in autograd like color and invdepth.  return_alpha (or an image
     bg) does not change color, except with no Gaussian at all (P == 0): the plain call then returns zeros like
-    upstream, this one the background (forward_raw)."""
+    upstream, this one the background (forward_raw).
+    absgrad=True: the backward also sets means2D.absgrad (P,3) = (sum over the Gaussian's pixels of |the pixel's
+    contribution to means2D.grad[:, :2]|, 0), the AbsGS densification criterion, as gsplat's absgrad does; it is
+    assigned (not accumulated) by every backward, and means2D.grad is what it is without."""
     rs = raster_settings
     camera = (rs.viewmatrix, rs.projmatrix, rs.campos)
     if not (torch.is_grad_enabled() and all(torch.is_tensor(t) for t in camera)
@@ -493,7 +540,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         camera = ()  # the call as it is without camera gradients
     bg = rs.bg if (torch.is_grad_enabled() and torch.is_tensor(rs.bg) and rs.bg.requires_grad) else None
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, bool(return_alpha), bg, *camera)
+                                     cov3Ds_precomp, raster_settings, bool(return_alpha), bool(absgrad), bg, *camera)
 
 
 def sh_backward_views(means3D: torch.Tensor, campos: torch.Tensor, dcolors_sh: torch.Tensor, sh_degree: int, M: int,
@@ -541,12 +588,15 @@ def mark_visible(positions: torch.Tensor, viewmatrix: torch.Tensor, projmatrix: 
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings, return_alpha: bool = False):
+    def __init__(self, raster_settings: GaussianRasterizationSettings, return_alpha: bool = False,
+                 absgrad: bool = False):
         """return_alpha=True: the call returns (color, radii, invdepth, alpha (1,H,W)); with P == 0 its color is the
-        background where the plain call's is zero (rasterize_gaussians)."""
+        background where the plain call's is zero (rasterize_gaussians).  absgrad=True: the backward sets
+        means2D.absgrad (rasterize_gaussians)."""
         super().__init__()
         self.raster_settings = raster_settings
         self.return_alpha = bool(return_alpha)
+        self.absgrad = bool(absgrad)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         with torch.no_grad():
@@ -562,4 +612,4 @@ class GaussianRasterizer(nn.Module):
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, rs, return_alpha=self.return_alpha)
+                                   cov3D_precomp, rs, return_alpha=self.return_alpha, absgrad=self.absgrad)

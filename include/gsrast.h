@@ -199,6 +199,31 @@ int gsr_forward_ext(gsr_forward_args *args, const gsr_composite_ext *ext, gsr_al
 int gsr_backward_ext(const gsr_backward_args *args, const gsr_composite_ext *ext, gsr_alloc_fn alloc, void *alloc_ctx,
                      void *stream);
 
+/* Absolute screen-space gradients for densification (AbsGS; `absgrad` in gsplat): a second side struct, versioned by
+ * its own size like gsr_composite_ext, so gsr_backward_args, gsr_composite_ext and GSR_ABI_VERSION stay as they are.
+ *   dL_dmeans2D_abs[i] = (sum_pix |m_x(i,pix)|, sum_pix |m_y(i,pix)|), m(i,pix) being what pixel pix adds to
+ *     dL_dmeans2D[i][:2] in the compositing backward under every upstream gradient of the call (colour, inverse depth,
+ *     gsr_composite_ext's dL_dalpha and background), in dL_dmeans2D's units.  The signed sum lets the contributions of
+ *     a Gaussian that is too bright on one side and too dark on the other cancel; this one does not.  Exactly 0 for a
+ *     Gaussian that is culled or that no pixel takes.  Summed in the fixed order of the other gradients (no float
+ *     atomics): two calls give the same bits, and every other output keeps the bits it has without this struct.
+ *   densify_abs != 0: args->densify_stats[i][0] is formed from this vector instead of from dL_dmeans2D[i][:2], as
+ *     sqrt(x * x + y * y) with each operation rounded once; [i][1], densify_accumulate and max_radii2D are unchanged.
+ *     GSR_ERR_ARG, before any device work, without args->densify_stats or without dL_dmeans2D_abs.
+ * Stages: the rows are produced by GSR_BWD_ALL and GSR_BWD_COMPOSITE whenever dL_dmeans2D_abs is non-NULL (the
+ * composite-only call does not write through it: the pointer is the request), into a GSR_BUF_BWD_SCRATCH buffer of
+ * gsr_bwd_scratch_bytes_abs bytes; GSR_BWD_ALL and GSR_BWD_GAUSSIANS write the output, the latter for Gaussians
+ * [g_begin, g_end) through a pointer that addresses Gaussian g_begin's row, from the scratch buffer of a composite call
+ * that was given the struct (with the same num_big).  With P = 0 nothing is written. */
+typedef struct gsr_absgrad_ext {
+    size_t struct_size;       /* sizeof as the caller was built; fields past it are read as NULL / 0 */
+    float *dL_dmeans2D_abs;   /* (P,2), fully written, or NULL */
+    int densify_abs;          /* densify_stats[:,0] from the absolute sums */
+} gsr_absgrad_ext;
+/* gsr_backward / gsr_backward_ext are this with absgrad = NULL (and ext = NULL). */
+int gsr_backward_abs(const gsr_backward_args *args, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
+                     gsr_alloc_fn alloc, void *alloc_ctx, void *stream);
+
 /* Multi-view SH gradient from compact per-view factors (no counterpart in the reference, whose batch size is
  * one view: gs_lightning_module.py:139-141).  dL_dsh[g] = sum_v basis(normalize(means3D[g] - campos[v]))
  * (x) dL_dcolors_sh[v][g], i.e. the sum over views of gsr_backward's dL_dsh -- what an all-reduce of dL_dsh
@@ -360,6 +385,7 @@ size_t gsr_geom_buffer_bytes(int P);
 size_t gsr_binning_buffer_bytes(int64_t R, int W, int H);
 size_t gsr_image_buffer_bytes(int W, int H);
 size_t gsr_bwd_scratch_bytes(int64_t R, int64_t num_big);
+size_t gsr_bwd_scratch_bytes_abs(int64_t R, int64_t num_big); /* with gsr_absgrad_ext.dL_dmeans2D_abs */
 
 /* Byte offsets of the internal arrays inside the three forward buffers (host arithmetic only).  Used by
  * the parity tests to compare the integer binning state (sorted instance list, tile ranges,
