@@ -69,6 +69,17 @@ class AbsgradExt(ctypes.Structure):  # include/gsrast.h gsr_absgrad_ext (version
         super().__init__(struct_size=ctypes.sizeof(AbsgradExt), **fields)
 
 
+class FeaturesExt(ctypes.Structure):  # include/gsrast.h gsr_features_ext (versioned by struct_size)
+    _fields_ = [("struct_size", ctypes.c_size_t), ("C", ctypes.c_int), ("features", _fp), ("out_features", _fp),
+                ("dL_dout_features", _fp), ("dL_dfeatures", _fp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=ctypes.sizeof(FeaturesExt), **fields)
+
+
+FEATURES_MAX_C = 64  # include/gsrast.h gsr_features_ext.C
+
+
 class AdamGroup(ctypes.Structure):
     _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("n", ctypes.c_int64),
                 ("lr", ctypes.c_double), ("step", ctypes.c_int64)]
@@ -132,6 +143,7 @@ EXPORTED_SYMBOLS = (
     "gsr_densify_workspace_bytes", "gsr_densify_classify", "gsr_densify_apply", "gsr_ply_unpack", "gsr_ply_pack",
     "gsr_knn_workspace_bytes", "gsr_knn_mean_dist2", "gsr_debug_wave_stamps",
     "gsr_forward_ext", "gsr_backward_ext", "gsr_backward_abs", "gsr_bwd_scratch_bytes_abs",
+    "gsr_forward_features", "gsr_backward_features", "gsr_bwd_scratch_bytes_features",
 )
 
 _lib = None
@@ -166,6 +178,17 @@ def load(path: str | None = None):
         lib.gsr_backward_abs.restype = ctypes.c_int
         lib.gsr_bwd_scratch_bytes_abs.argtypes = [ctypes.c_int64, ctypes.c_int64]
         lib.gsr_bwd_scratch_bytes_abs.restype = ctypes.c_size_t
+    if hasattr(lib, "gsr_forward_features"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
+        lib.gsr_forward_features.argtypes = [ctypes.POINTER(ForwardArgs), ctypes.POINTER(CompositeExt),
+                                             ctypes.POINTER(FeaturesExt), ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.POINTER(ctypes.c_int64)]
+        lib.gsr_forward_features.restype = ctypes.c_int
+        lib.gsr_backward_features.argtypes = [ctypes.POINTER(BackwardArgs), ctypes.POINTER(CompositeExt),
+                                              ctypes.POINTER(AbsgradExt), ctypes.POINTER(FeaturesExt), ALLOC_FN,
+                                              ctypes.c_void_p, ctypes.c_void_p]
+        lib.gsr_backward_features.restype = ctypes.c_int
+        lib.gsr_bwd_scratch_bytes_features.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
+        lib.gsr_bwd_scratch_bytes_features.restype = ctypes.c_size_t
     lib.gsr_mark_visible.argtypes = [ctypes.c_int, _fp, _fp, _fp, _fp, ctypes.c_void_p]
     lib.gsr_mark_visible.restype = ctypes.c_int
     lib.gsr_sh_backward_views.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp,

@@ -82,13 +82,16 @@ enum Stage {
     ST_SEG_SORT,
     ST_ADAM_SH,
     ST_BACKGROUND_GRAD,
+    ST_FEAT_FWD,
+    ST_FEAT_BWD,
+    ST_FEAT_GATHER,
     ST_COUNT
 };
 const char *kStageNames[ST_COUNT] = {"preprocess", "depth_sort", "instance_scan", "readback",
                                      "expand",     "tile_sort",  "tile_ranges",   "render_fwd",
                                      "render_bwd", "big_reduce", "preprocess_bwd", "sh_views",
                                      "bucket_count", "bucket_scatter", "seg_sort", "adam_sh_views",
-                                     "background_grad"};
+                                     "background_grad", "feat_fwd", "feat_bwd", "feat_gather"};
 
 struct Profiler {
     std::mutex mu;
@@ -404,6 +407,34 @@ void read_absgrad_ext(const gsr_absgrad_ext *x, AbsgradExt &e) {
         e.densify_abs = full.densify_abs;
 }
 
+// gsr_features_ext as the library reads it: a field the caller's struct does not cover whole is NULL
+struct FeaturesExt {
+    bool given = false;
+    int C = 0;
+    const float *features = nullptr;
+    float *out_features = nullptr;
+    const float *dL_dout_features = nullptr;
+    float *dL_dfeatures = nullptr;
+};
+// the checks both directions share: the struct's size, C and the features pointer
+int read_features_ext(const gsr_features_ext *x, int P, FeaturesExt &f) {
+    if (!x) return GSR_OK;
+    if (x->struct_size < offsetof(gsr_features_ext, features) + sizeof(x->features))
+        return fail(GSR_ERR_ARG, "gsr_features_ext: struct_size ends before the first pointer field");
+    gsr_features_ext full{};
+    memcpy(&full, x, std::min(x->struct_size, sizeof(full)));
+    auto has = [&](size_t off) { return off + sizeof(void *) <= x->struct_size; };
+    f.given = true;
+    f.C = full.C;
+    f.features = full.features;
+    if (has(offsetof(gsr_features_ext, out_features))) f.out_features = full.out_features;
+    if (has(offsetof(gsr_features_ext, dL_dout_features))) f.dL_dout_features = full.dL_dout_features;
+    if (has(offsetof(gsr_features_ext, dL_dfeatures))) f.dL_dfeatures = full.dL_dfeatures;
+    if (f.C < 1 || f.C > FEAT_MAX_C) return fail(GSR_ERR_ARG, "gsr_features_ext: C must be in [1, 64]");
+    if (P > 0 && !f.features) return fail(GSR_ERR_ARG, "gsr_features_ext: features is required");
+    return GSR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -423,6 +454,9 @@ size_t gsr_image_buffer_bytes(int W, int H) {
 }
 size_t gsr_bwd_scratch_bytes(int64_t R, int64_t num_big) { return bwd_scratch_bytes(R, num_big); }
 size_t gsr_bwd_scratch_bytes_abs(int64_t R, int64_t num_big) { return bwd_scratch_bytes_abs(R, num_big); }
+size_t gsr_bwd_scratch_bytes_features(int64_t R, int64_t num_big, int C) {
+    return (C < 1 || C > FEAT_MAX_C) ? 0 : bwd_scratch_bytes_features(R, num_big, feat_block(C));
+}
 
 void gsr_state_layout_query(int P, int64_t R, int W, int H, gsr_state_layout *caller) {
     if (!caller) return;
@@ -473,10 +507,19 @@ int gsr_forward(gsr_forward_args *a, gsr_alloc_fn alloc, void *alloc_ctx, void *
 
 int gsr_forward_ext(gsr_forward_args *a, const gsr_composite_ext *ext, gsr_alloc_fn alloc, void *alloc_ctx,
                     void *stream_ptr, int64_t *num_rendered) {
+    return gsr_forward_features(a, ext, nullptr, alloc, alloc_ctx, stream_ptr, num_rendered);
+}
+
+int gsr_forward_features(gsr_forward_args *a, const gsr_composite_ext *ext, const gsr_features_ext *feat,
+                         gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr, int64_t *num_rendered) {
     if (!a || !alloc || !num_rendered) return fail(GSR_ERR_ARG, "null argument");
     CompositeExt e;
     int rc = read_composite_ext(ext, a->background, e);
     if (rc) return rc;
+    FeaturesExt fx;
+    rc = read_features_ext(feat, a->P, fx);
+    if (rc) return rc;
+    if (fx.given && !fx.out_features) return fail(GSR_ERR_ARG, "gsr_features_ext: out_features is required");
     rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
                       a->scales, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
                       e.background_image ? e.background_image : a->background);
@@ -500,6 +543,7 @@ int gsr_forward_ext(gsr_forward_args *a, const gsr_composite_ext *ext, gsr_alloc
             GSR_HIP(hipMemsetAsync(a->out_color, 0, sizeof(float) * 3 * (size_t)W * H, stream));
         }
         if (a->out_invdepth) GSR_HIP(hipMemsetAsync(a->out_invdepth, 0, sizeof(float) * (size_t)W * H, stream));
+        if (fx.given) GSR_HIP(hipMemsetAsync(fx.out_features, 0, sizeof(float) * fx.C * (size_t)W * H, stream));
         return GSR_OK;
     }
 
@@ -781,6 +825,13 @@ int gsr_forward_ext(gsr_forward_args *a, const gsr_composite_ext *ext, gsr_alloc
     if (R > 0 && (!rp.point_list || !rp.inst_gid || !rp.sorted_u))
         return fail(GSR_ERR_ARG, "internal: composite buffer not set");
     GSR_STAGE(ST_RENDER_FWD, dbg, launch_render_fwd(stream, rp));
+    if (fx.given) {  // the feature image, replayed from what the composite just recorded (tile_last = 0: zeros)
+        FeatFwdParams fp;
+        fp.W = W; fp.H = H; fp.gx = gx; fp.gy = gy; fp.num_tiles = (int)T; fp.C = fx.C;
+        fp.ranges = im.ranges; fp.point_list = b.point_list; fp.n_contrib = im.n_contrib; fp.tile_last = im.tile_last;
+        fp.rec = g.rec; fp.features = fx.features; fp.out = fx.out_features; fp.strip_exact = 1;
+        GSR_STAGE(ST_FEAT_FWD, dbg, launch_feat_fwd(stream, fp));
+    }
     (void)depth_onesweep;
     (void)tile_onesweep;
     if (dbg)  // every radix sort clears its error word (onesweep: with its control block; multi-kernel: pass 0)
@@ -871,12 +922,26 @@ int gsr_backward_ext(const gsr_backward_args *a, const gsr_composite_ext *ext, g
 
 int gsr_backward_abs(const gsr_backward_args *a, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
                      gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr) {
+    return gsr_backward_features(a, ext, absgrad, nullptr, alloc, alloc_ctx, stream_ptr);
+}
+
+int gsr_backward_features(const gsr_backward_args *a, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
+                          const gsr_features_ext *feat, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr) {
     if (!a || !alloc) return fail(GSR_ERR_ARG, "null argument");
     CompositeExt e;
     int rc = read_composite_ext(ext, a->background, e);
     if (rc) return rc;
     AbsgradExt ab;
     read_absgrad_ext(absgrad, ab);
+    FeaturesExt fx;
+    rc = read_features_ext(feat, a->P, fx);
+    if (rc) return rc;
+    if (fx.given && ab.dL_dmeans2D_abs)
+        return fail(GSR_ERR_UNSUPPORTED, "features with gsr_absgrad_ext.dL_dmeans2D_abs are not built yet");
+    if (fx.given && a->stages != GSR_BWD_ALL)
+        return fail(GSR_ERR_UNSUPPORTED, "features with a split backward (stages != GSR_BWD_ALL) are not built yet");
+    // the feature work of this call: only with an upstream gradient of the feature image
+    const bool feat_bwd = fx.given && fx.dL_dout_features != nullptr;
     if (ab.densify_abs && !a->densify_stats)
         return fail(GSR_ERR_ARG, "gsr_absgrad_ext.densify_abs needs densify_stats");
     if (ab.densify_abs && !ab.dL_dmeans2D_abs)
@@ -932,8 +997,9 @@ int gsr_backward_abs(const gsr_backward_args *a, const gsr_composite_ext *ext, c
     const uint32_t nbig = nbig_on_device ? R / (BIG_GAUSSIAN_TILES + 1) + 1 : (uint32_t)a->num_big;
     char *scratch = a->stages == GSR_BWD_GAUSSIANS ? a->bwd_scratch
                                                    : alloc(alloc_ctx, GSR_BUF_BWD_SCRATCH,
-                                                           ab.dL_dmeans2D_abs ? bwd_scratch_bytes_abs(R, nbig)
-                                                                              : bwd_scratch_bytes(R, nbig));
+                                                           feat_bwd ? bwd_scratch_bytes_features(R, nbig, feat_block(fx.C))
+                                                           : ab.dL_dmeans2D_abs ? bwd_scratch_bytes_abs(R, nbig)
+                                                                                : bwd_scratch_bytes(R, nbig));
     if (!scratch && a->stages != GSR_BWD_GAUSSIANS) return fail(GSR_ERR_ALLOC, "backward scratch allocation failed");
     float *rows = reinterpret_cast<float *>(scratch);
     // Gaussian-major gradient rows: render_bwd scatters its 40-B rows to the instances' expansion indices so
@@ -979,6 +1045,32 @@ int gsr_backward_abs(const gsr_backward_args *a, const gsr_composite_ext *ext, c
         }
         if (a->stages == GSR_BWD_ALL && tuning("bwd_prezero", 1)) prezero = zero_fill_plan(a, ab.dL_dmeans2D_abs, g0, g1, rp);
         GSR_STAGE(ST_RENDER_BWD, dbg, launch_render_bwd(stream, rp));
+        if (feat_bwd) {
+            // Channel block after channel block: the walk adds the block's geometry terms into the rows render_bwd just
+            // wrote (and marks the live flags), then the block's feature rows are gathered into dL_dfeatures, so one
+            // block's rows are all the scratch there is.  big_reduce below then sums rows that hold every term.
+            const int fb = feat_block(fx.C);
+            FeatBwdParams fp;
+            fp.W = W; fp.H = H; fp.gx = gx; fp.gy = gy; fp.num_tiles = (int)T; fp.C = fx.C;
+            fp.ranges = im.ranges; fp.point_list = b.point_list; fp.n_contrib = im.n_contrib;
+            fp.tile_last = im.tile_last; fp.tile_loaded = im.tile_loaded; fp.sorted_u = b.sorted_u;
+            fp.rec = g.rec; fp.final_T = im.final_T; fp.features = fx.features; fp.dL_dF = fx.dL_dout_features;
+            fp.rows = rows; fp.frows = reinterpret_cast<float *>(bwd_feat_rows_ptr(scratch, R, nbig));
+            fp.live = rp.live; fp.strip_exact = 1;
+            FeatGatherParams gp;
+            gp.P = P; gp.C = fx.C;
+            gp.radii = a->radii; gp.tiles = g.tiles; gp.inst_start = g.inst_start; gp.big_slot = g.big_slot;
+            gp.big_list = g.big_list; gp.inv = b.inv;
+            gp.live = rp.live; gp.live_valid = rp.live_valid;
+            gp.frows = fp.frows; gp.bigsum = reinterpret_cast<float *>(bwd_feat_bigsum_ptr(scratch, R, nbig, fb));
+            gp.nbig = nbig; gp.nbig_dev = nbig_on_device ? g.counters + CNT_BIG : nullptr;
+            gp.out = fx.dL_dfeatures;
+            for (int c0 = 0; c0 < fx.C; c0 += fb) {
+                fp.c0 = gp.c0 = c0;
+                GSR_STAGE(ST_FEAT_BWD, dbg, launch_feat_bwd(stream, fp));
+                if (gp.out) GSR_STAGE(ST_FEAT_GATHER, dbg, launch_feat_gather(stream, gp));
+            }
+        }
         BigReduceParams bp;
         bp.big_list = g.big_list; bp.inst_start = g.inst_start; bp.tiles = g.tiles;
         bp.inv = b.inv;
@@ -991,6 +1083,8 @@ int gsr_backward_abs(const gsr_backward_args *a, const gsr_composite_ext *ext, c
         rc = background_grads(a, e, im.final_T, alloc, alloc_ctx, stream);
         if (rc) return rc;
     }
+    if (fx.dL_dfeatures && !(feat_bwd && R > 0))  // no upstream gradient, or nothing rendered: the empty sums
+        GSR_HIP(hipMemsetAsync(fx.dL_dfeatures, 0, sizeof(float) * (size_t)P * fx.C, stream));
     if (a->stages == GSR_BWD_COMPOSITE) return GSR_OK;
     // Chunk-relative outputs (a split backward) address Gaussian g0's row: shift them so the kernel indexes every
     // output by the absolute Gaussian index (integer arithmetic: the shifted address is never dereferenced)

@@ -359,6 +359,16 @@ inline char *bwd_abs_rows_ptr(char *scratch, int64_t R, int64_t nbig) { return s
 inline char *bwd_abs_bigsum_ptr(char *scratch, int64_t R, int64_t nbig) {
     return bwd_abs_rows_ptr(scratch, R, nbig) + align_up((size_t)(R ? R : 1) * 2 * sizeof(float), 256);
 }
+// with feature channels: behind the plain layout (unchanged), ONE channel block's feature rows (fb = 8 or 16 floats
+// per instance; the blocks are processed one after the other and reuse them), then one such row per big Gaussian
+inline size_t bwd_scratch_bytes_features(int64_t R, int64_t nbig, int fb) {
+    return bwd_scratch_bytes(R, nbig) + align_up((size_t)(R ? R : 1) * fb * sizeof(float), 256) +
+           align_up((size_t)(nbig ? nbig : 1) * fb * sizeof(float), 256);
+}
+inline char *bwd_feat_rows_ptr(char *scratch, int64_t R, int64_t nbig) { return scratch + bwd_scratch_bytes(R, nbig); }
+inline char *bwd_feat_bigsum_ptr(char *scratch, int64_t R, int64_t nbig, int fb) {
+    return bwd_feat_rows_ptr(scratch, R, nbig) + align_up((size_t)(R ? R : 1) * fb * sizeof(float), 256);
+}
 inline float *bwd_bigsum_ptr(char *scratch, int64_t R) {
     return reinterpret_cast<float *>(scratch + align_up((size_t)(R ? R : 1) * GRAD_ROW * sizeof(float), 256));
 }

@@ -1,0 +1,457 @@
+// gsr_features.hip -- per-Gaussian feature channels (gsr_features_ext): features (P,C) composited with the colour
+// render's weights w_i(pix) = alpha_i T_i into out_features (C,H,W), and their backward.
+//
+// Kernels of their own beside render_fwd_v6_kernel / render_bwd_v5_kernel (both at their register budgets), so a call
+// without features launches exactly what it launched before.  All three read only what the colour forward recorded
+// (point_list, ranges, n_contrib, final_T, tile_last / tile_loaded, the 48-B render records) and evaluate alpha with the
+// composite's staged-record arithmetic (stage_rec_a/b, power2_at, v_exp_f32, min(0.99, o G), the power > 0 and
+// alpha < 1/255 skips, and under the "guard" knob its guarded decision), so the decisions and the weights are those of
+// the colour forward.
+//
+// Channel blocks: a launch carries FB = 8 (C <= 8) or 16 channels of the C; the walk is repeated per block.  The
+// forward's blocks are independent (grid.y); the backward's run one launch after the other, because each ADDS its
+// geometry terms into the instance's 40-B gradient row: only the projection g = sum_c f_ic dL/dF_c(pix) of a
+// Gaussian's channels onto the pixel's upstream gradient enters dL/dalpha, the scalar "behind" accumulator follows
+// D <- D + alpha (g - D) from 0 (no background term), and both are linear in dL/dF, so a block's six moment sums are
+// formed with its own D and added.  One wave owns a tile's rows: a plain read-add-store, no atomics.
+#include "gsr_kernels.h"
+
+namespace gsr {
+
+constexpr int FEAT_BATCH = 32;
+
+int feat_block(int C) { return C <= 8 ? 8 : 16; }
+
+// One batch's records, Gaussian ids and strip masks: lane j < cnt stages the instance at sorted position s0 + j * step
+// (step = +1 front to back, -1 back to front).  Returns the lane's 4-bit strip mask (cell_mask: conservative, a strip
+// without its bit holds no pixel that passes the alpha test).
+__device__ __forceinline__ uint32_t feat_stage(const GRec *__restrict__ rec, const uint32_t *__restrict__ point_list,
+                                               uint32_t s_me, bool mine, int lane, FwdRec *s_rec, uint32_t *s_gid,
+                                               bool strip_exact, float row0, float col0, float4 &raw_a, float4 &raw_b) {
+    uint32_t m = 0;
+    if (mine) {
+        const uint32_t gid = point_list[s_me];
+        s_gid[lane] = gid;
+        raw_a = rec[gid].a;
+        raw_b = rec[gid].b;
+        s_rec[lane].a = stage_rec_a(raw_a);
+        s_rec[lane].b = stage_rec_b(raw_b);
+        m = cell_mask(strip_exact, raw_a, raw_b, row0, col0);
+    }
+    return m;
+}
+
+// The batch's feature rows, channels [c0, c0 + FB) (zero past C), into LDS: 4-B loads only -- a row of (P,C) with odd C
+// is not 16-B aligned.
+template <int FB>
+__device__ __forceinline__ void feat_load_rows(const float *__restrict__ features, int C, int c0, int cnt, int lane,
+                                               const uint32_t *s_gid, float (*s_f)[FB]) {
+    for (int e = lane; e < cnt * FB; e += 64) {
+        const int j = e / FB, c = e % FB;
+        s_f[j][c] = c0 + c < C ? features[(size_t)s_gid[j] * C + (c0 + c)] : 0.f;
+    }
+}
+
+// The composite's alpha decision for one (pixel, instance) pair: power <= 0 and alpha >= 1/255.  GUARD ("guard" knob):
+// the forward's guarded decision (gsr_common.h) -- a pair whose alpha lies in the band around 1/255 is re-decided from
+// the oracle's own arithmetic on the raw record, exactly as render_fwd_v6_kernel / render_bwd_v5_kernel do, so the
+// replay takes the pairs the guarded colour forward took.
+template <bool GUARD>
+__device__ __forceinline__ bool feat_alpha_pass(float power2, float alpha, const GRec *__restrict__ rec, uint32_t gid,
+                                                float pfx, float pfy) {
+    if constexpr (GUARD) {
+        if (!(power2 <= 0.0f) || !(alpha >= GUARD_A_LO)) return false;
+        if (alpha >= GUARD_A_HI) return true;
+        return guard_alpha_pass(rec, gid, pfx, pfy);  // rare
+    } else {
+        return power2 <= 0.0f && !(alpha < 1.0f / 255.0f);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Feature forward (replay): one wave per (tile, channel block), 4 pixels per lane as the composite.  Walks
+// point_list[ranges[tile]] up to each pixel's n_contrib; T restarts from 1 and follows the forward's T (1 - alpha),
+// the weight is its alpha T and the sum its fmaf(value, weight, sum) in the same order, so with the same values the
+// image has the colour image's bits.
+// ------------------------------------------------------------------------------------------------
+template <int FB, bool GUARD = false>
+__global__ __launch_bounds__(64) void feat_fwd_kernel(FeatFwdParams p) {
+    __shared__ FwdRec s_rec[FEAT_BATCH];
+    __shared__ uint32_t s_gid[FEAT_BATCH];
+    __shared__ __attribute__((aligned(16))) float s_f[FEAT_BATCH][FB];
+    const int lane = threadIdx.x;
+    const int tile = blockIdx.x, c0 = (int)blockIdx.y * FB;
+    const int tx = tile % p.gx, ty = tile / p.gx;
+    const int px = tx * BLOCK_X + (lane & 15);
+    const int py0 = ty * BLOCK_Y + (lane >> 4);
+    const float pfx = (float)px;
+    const float row0 = (float)(ty * BLOCK_Y), col0 = (float)(tx * BLOCK_X);
+    const uint32_t r0 = __builtin_amdgcn_readfirstlane(p.ranges[tile].x);
+    const uint32_t tl = __builtin_amdgcn_readfirstlane(p.tile_last[tile]);
+    float T[PIX_PER_LANE], prow[PIX_PER_LANE], F[PIX_PER_LANE][FB];
+    uint32_t lastc[PIX_PER_LANE];
+#pragma unroll
+    for (int k = 0; k < PIX_PER_LANE; k++) {
+        const int py = py0 + 4 * k;
+        const bool inside = px < p.W && py < p.H;
+        lastc[k] = inside ? p.n_contrib[(size_t)py * p.W + px] : 0u;
+        T[k] = 1.0f;
+        prow[k] = (float)py;
+#pragma unroll
+        for (int c = 0; c < FB; c++) F[k][c] = 0.f;
+    }
+    for (uint32_t b0 = 0; b0 < tl; b0 += FEAT_BATCH) {
+        const int cnt = (int)min((uint32_t)FEAT_BATCH, tl - b0);
+        float4 ra, rb;
+        const uint32_t my_m = feat_stage(p.rec, p.point_list, r0 + b0 + (uint32_t)lane, lane < cnt, lane, s_rec, s_gid,
+                                         p.strip_exact != 0, row0, col0, ra, rb);
+        uint64_t sk[PIX_PER_LANE], un = 0;
+#pragma unroll
+        for (int k = 0; k < PIX_PER_LANE; k++) {
+            sk[k] = __ballot((my_m >> k) & 1u);
+            un |= sk[k];
+        }
+        wave_lds_sync();
+        feat_load_rows<FB>(p.features, p.C, c0, cnt, lane, s_gid, s_f);
+        wave_lds_sync();
+        while (un) {  // the instances that reach a strip, front to back
+            const int j = (int)__builtin_ctzll(un);
+            un &= ~(1ull << j);
+            const uint32_t idx = b0 + (uint32_t)j;
+            const float4 a = s_rec[j].a, b = s_rec[j].b;  // a: x, y, A, B; b: C, o, -, -
+            float f[FB];
+#pragma unroll
+            for (int c = 0; c < FB; c += 4) {
+                const float4 v = *reinterpret_cast<const float4 *>(&s_f[j][c]);
+                f[c] = v.x, f[c + 1] = v.y, f[c + 2] = v.z, f[c + 3] = v.w;
+            }
+            const float dx = a.x - pfx;
+            const float P0 = (a.z * dx) * dx, L = a.w * dx;
+#pragma unroll
+            for (int k = 0; k < PIX_PER_LANE; k++) {
+                if (!((sk[k] >> j) & 1u)) continue;  // wave-uniform
+                const float power2 = power2_at(b.x, a.y - prow[k], P0, L);
+                const float alpha = fminf(0.99f, b.y * __builtin_amdgcn_exp2f(power2));
+                if (idx < lastc[k] && feat_alpha_pass<GUARD>(power2, alpha, p.rec, s_gid[j], pfx, prow[k])) {
+                    const float wgt = alpha * T[k];
+#pragma unroll
+                    for (int c = 0; c < FB; c++) F[k][c] = fmaf(f[c], wgt, F[k][c]);
+                    T[k] = T[k] * (1 - alpha);
+                }
+            }
+        }
+        wave_lds_sync();  // the next batch overwrites the staged records and rows
+    }
+    const size_t HW = (size_t)p.W * p.H;
+#pragma unroll
+    for (int k = 0; k < PIX_PER_LANE; k++) {
+        const int py = py0 + 4 * k;
+        if (px < p.W && py < p.H) {
+            const size_t pid = (size_t)py * p.W + px;
+#pragma unroll
+            for (int c = 0; c < FB; c++)
+                if (c0 + c < p.C) p.out[(size_t)(c0 + c) * HW + pid] = F[k][c];
+        }
+    }
+}
+
+void launch_feat_fwd(hipStream_t s, const FeatFwdParams &p0) {
+    if (p0.num_tiles <= 0 || p0.C <= 0) return;
+    FeatFwdParams p = p0;
+    p.strip_exact = tuning("strip_exact", 1);
+    const int fb = feat_block(p.C);
+    const dim3 grid((uint32_t)p.num_tiles, (uint32_t)div_up((uint32_t)p.C, (uint32_t)fb)), block(64);
+    if (tuning("guard", 0)) {  // the colour forward ran with the guard: the same decisions
+        if (fb == 8) feat_fwd_kernel<8, true><<<grid, block, 0, s>>>(p);
+        else feat_fwd_kernel<16, true><<<grid, block, 0, s>>>(p);
+        return;
+    }
+    if (fb == 8) feat_fwd_kernel<8><<<grid, block, 0, s>>>(p);
+    else feat_fwd_kernel<16><<<grid, block, 0, s>>>(p);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Transposing wave reduction of NV (16 or 32) per-lane values, a plainer relative of wave_reduce_pair_store: each
+// level halves the number of values a lane carries by exchanging one half with the partner lane across one lane bit
+// (bit 5: v_permlane32_swap, bit 4: v_permlane16_swap, bit 3: row_ror:8, bit 2: row_half_mirror -- whose partner
+// 7 - l also flips bits 0 and 1, which the last two levels sum over anyway -- bit 1: quad_perm [2,3,0,1]), and the
+// levels left over are plain DPP adds.  Value n's total over the 64 lanes lands in the lanes whose bits spell n
+// (n = b5 + 2 b4 + 4 b3 + 8 b2 [+ 16 b1]) and is stored to dst[n].  A fixed tree: bitwise reproducible.  Every lane
+// must be active.
+// ------------------------------------------------------------------------------------------------
+template <int NV>
+__device__ __forceinline__ void wave_reduce_store(const float *v, float *__restrict__ dst, int lane) {
+    static_assert(NV == 16 || NV == 32, "16 or 32 values");
+    float a[NV / 2], b[NV / 4], c[NV / 8], d[NV / 16];
+#pragma unroll
+    for (int i = 0; i < NV / 2; i++) a[i] = sum_swap32(v[2 * i], v[2 * i + 1]);
+#pragma unroll
+    for (int i = 0; i < NV / 4; i++) b[i] = sum_swap16(a[2 * i], a[2 * i + 1]);
+    const bool h3 = (lane & 8) != 0, h2 = (lane & 4) != 0, h1 = (lane & 2) != 0;
+#pragma unroll
+    for (int i = 0; i < NV / 8; i++) {
+        const float keep = h3 ? b[2 * i + 1] : b[2 * i], send = h3 ? b[2 * i] : b[2 * i + 1];
+        c[i] = dpp_xadd<0x128>(keep, send);  // row_ror:8 (= lane ^ 8)
+    }
+#pragma unroll
+    for (int i = 0; i < NV / 16; i++) {
+        const float keep = h2 ? c[2 * i + 1] : c[2 * i], send = h2 ? c[2 * i] : c[2 * i + 1];
+        d[i] = dpp_xadd<0x141>(keep, send);  // row_half_mirror
+    }
+    int n = ((lane >> 5) & 1) | ((lane >> 3) & 2) | ((lane >> 1) & 4) | ((lane << 1) & 8);
+    float e;
+    if constexpr (NV == 32) {
+        const float keep = h1 ? d[1] : d[0], send = h1 ? d[0] : d[1];
+        e = dpp_xadd<0x4E>(keep, send);  // quad_perm [2,3,0,1]
+        n |= (lane << 3) & 16;
+    } else {
+        e = dpp_add<0x4E>(d[0]);
+    }
+    e = dpp_add<0xB1>(e);  // quad_perm [1,0,3,2]
+    if ((lane & (NV == 32 ? 1 : 3)) == 0) dst[n] = e;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Feature compositing backward: one wave per tile, one channel block per launch (launched after render_bwd and before
+// big_reduce).  The reverse walk of render_bwd: T recovered by T / (1 - alpha) from final_T, one scalar D per pixel from
+// 0.  Per contributing (pixel, instance): g = sum_c f_ic dL/dF_c, d = g - D, D <- D + alpha d, q = G d T, and the lane
+// accumulates q, q dy, q dy^2 and the block's FB feature weights w dL/dF_c.  Per instance the wave reduces the six
+// moments (q, q dx, q dy, q dx^2, q dx dy, q dy^2) and the FB weights together (wave_reduce_store).  After a batch, lane
+// j converts instance j's moments to the row's dmean2D / dconic / dopacity form (render_bwd's conversion) and adds
+// them to rows[sorted_u[s]][0..5] -- the four weight floats of the row stay -- and the wave stores the FB feature
+// weights to frows[sorted_u[s]], the block's scratch rows by expansion index.  live[gid] = 1 for every Gaussian whose
+// row or feature row it makes non-zero: preprocess_bwd and the gathers skip the others.
+// ------------------------------------------------------------------------------------------------
+template <int FB, bool GUARD = false>
+__global__ __launch_bounds__(64) void feat_bwd_kernel(FeatBwdParams p) {
+    constexpr int NV = FB + 6 <= 16 ? 16 : 32;
+    __shared__ FwdRec s_rec[FEAT_BATCH];
+    __shared__ uint32_t s_gid[FEAT_BATCH];
+    __shared__ uint32_t s_row[FEAT_BATCH];
+    __shared__ __attribute__((aligned(16))) float s_f[FEAT_BATCH][FB];
+    __shared__ __attribute__((aligned(16))) float s_red[FEAT_BATCH][NV];
+    const int lane = threadIdx.x;
+    const int tile = blockIdx.x, c0 = p.c0;
+    const int tx = tile % p.gx, ty = tile / p.gx;
+    const int px = tx * BLOCK_X + (lane & 15);
+    const int py0 = ty * BLOCK_Y + (lane >> 4);
+    const float pfx = (float)px;
+    const float row0 = (float)(ty * BLOCK_Y), col0 = (float)(tx * BLOCK_X);
+    const uint32_t r0 = __builtin_amdgcn_readfirstlane(p.ranges[tile].x);
+    const uint32_t tl = __builtin_amdgcn_readfirstlane(p.tile_last[tile]);
+    const uint32_t loaded = __builtin_amdgcn_readfirstlane(p.tile_loaded[tile]);
+    // the instances the forward loaded but no pixel reached: zero feature rows (render_bwd zeroed their 40-B rows)
+    for (uint32_t e = (uint32_t)lane; e < (loaded > tl ? loaded - tl : 0u) * FB; e += 64)
+        p.frows[(size_t)p.sorted_u[r0 + tl + e / FB] * FB + e % FB] = 0.f;
+    if (tl == 0) return;
+
+    const size_t HW = (size_t)p.W * p.H;
+    float T[PIX_PER_LANE], D[PIX_PER_LANE], prow[PIX_PER_LANE], dF[PIX_PER_LANE][FB];
+    uint32_t lastc[PIX_PER_LANE];
+#pragma unroll
+    for (int k = 0; k < PIX_PER_LANE; k++) {
+        const int py = py0 + 4 * k;
+        const bool inside = px < p.W && py < p.H;
+        const size_t pid = inside ? (size_t)py * p.W + px : 0;
+        T[k] = inside ? p.final_T[pid] : 0.f;
+        lastc[k] = inside ? p.n_contrib[pid] : 0u;
+        D[k] = 0.f;
+        prow[k] = (float)py;
+#pragma unroll
+        for (int c = 0; c < FB; c++) dF[k][c] = (inside && c0 + c < p.C) ? p.dL_dF[(size_t)(c0 + c) * HW + pid] : 0.f;
+    }
+    const float hW = 0.5f * p.W, hH = 0.5f * p.H;
+
+    for (int bend = (int)tl; bend > 0; bend -= FEAT_BATCH) {
+        const int cnt = min(FEAT_BATCH, bend);
+        float4 my_a = make_float4(0, 0, 0, 0), my_b = my_a;
+        const uint32_t s_me = r0 + (uint32_t)(bend - 1 - lane);
+        const uint32_t my_m = feat_stage(p.rec, p.point_list, s_me, lane < cnt, lane, s_rec, s_gid, p.strip_exact != 0,
+                                         row0, col0, my_a, my_b);
+        if (lane < cnt) s_row[lane] = p.sorted_u[s_me];
+        uint64_t sk[PIX_PER_LANE], un = 0;
+#pragma unroll
+        for (int k = 0; k < PIX_PER_LANE; k++) {
+            sk[k] = __ballot((my_m >> k) & 1u);
+            un |= sk[k];
+        }
+        wave_lds_sync();
+        feat_load_rows<FB>(p.features, p.C, c0, cnt, lane, s_gid, s_f);
+        wave_lds_sync();
+        for (int j = 0; j < cnt; j++) {
+            bool any = false;
+            float m[NV];
+#pragma unroll
+            for (int v = 0; v < NV; v++) m[v] = 0.f;
+            if ((un >> j) & 1ull) {  // wave-uniform: the instance reaches a strip
+                const uint32_t idx = (uint32_t)(bend - 1 - j);
+                const float4 a = s_rec[j].a, b = s_rec[j].b;  // a: x, y, A, B; b: C, o, -, -
+                float f[FB];
+#pragma unroll
+                for (int c = 0; c < FB; c += 4) {
+                    const float4 v = *reinterpret_cast<const float4 *>(&s_f[j][c]);
+                    f[c] = v.x, f[c + 1] = v.y, f[c + 2] = v.z, f[c + 3] = v.w;
+                }
+                const float dx = a.x - pfx;
+                const float P0 = (a.z * dx) * dx, L = a.w * dx;
+                float Q0 = 0.f, Q1 = 0.f, Q2 = 0.f;
+#pragma unroll
+                for (int k = 0; k < PIX_PER_LANE; k++) {
+                    if (!((sk[k] >> j) & 1u)) continue;  // wave-uniform
+                    const float dy = a.y - prow[k];
+                    const float power2 = power2_at(b.x, dy, P0, L);
+                    const float G = __builtin_amdgcn_exp2f(power2);
+                    const float alpha = fminf(0.99f, b.y * G);
+                    if (idx < lastc[k] && feat_alpha_pass<GUARD>(power2, alpha, p.rec, s_gid[j], pfx, prow[k])) {
+                        any = true;
+                        T[k] = T[k] * fast_rcp(1.f - alpha);
+                        const float wgt = alpha * T[k];
+                        float g = 0.f;
+#pragma unroll
+                        for (int c = 0; c < FB; c++) {
+                            g = fmaf(f[c], dF[k][c], g);
+                            m[6 + c] = fmaf(wgt, dF[k][c], m[6 + c]);
+                        }
+                        const float d = g - D[k];
+                        D[k] = fmaf(alpha, d, D[k]);
+                        const float q = G * (d * T[k]);
+                        const float qdy = q * dy;
+                        Q0 += q;
+                        Q1 += qdy;
+                        Q2 = fmaf(qdy, dy, Q2);
+                    }
+                }
+                // the six moments in gradient-row order (S, Sx, Sy, Sxx, Sxy, Syy): dx is the lane's own
+                m[0] = Q0;
+                m[1] = Q0 * dx;
+                m[2] = Q1;
+                m[3] = m[1] * dx;
+                m[4] = Q1 * dx;
+                m[5] = Q2;
+            }
+            if (__ballot(any)) wave_reduce_store<NV>(m, s_red[j], lane);
+            else if (lane < NV) s_red[j][lane] = 0.f;
+        }
+        wave_lds_sync();
+        bool nz = false;
+        if (lane < cnt) {
+            const float *u = s_red[lane];
+            const float S = u[0], Sx = u[1], Sy = u[2], Sxx = u[3], Sxy = u[4], Syy = u[5];
+            const float o = my_b.y, ca = my_a.z, cb = my_a.w, cc = my_b.x;  // the raw record's opacity and conic
+            float add[6];
+            add[0] = -o * hW * (ca * Sx + cb * Sy);
+            add[1] = -o * hH * (cb * Sx + cc * Sy);
+            add[2] = -0.5f * o * Sxx;
+            add[3] = -0.5f * o * Sxy;
+            add[4] = -0.5f * o * Syy;
+            add[5] = S;
+            float2 *row = reinterpret_cast<float2 *>(p.rows + (size_t)s_row[lane] * GRAD_ROW);
+#pragma unroll
+            for (int h = 0; h < 3; h++) {
+                nz = nz || add[2 * h] != 0.f || add[2 * h + 1] != 0.f;
+                const float2 r = row[h];
+                row[h] = make_float2(r.x + add[2 * h], r.y + add[2 * h + 1]);
+            }
+#pragma unroll
+            for (int c = 0; c < FB; c++) nz = nz || u[6 + c] != 0.f;
+            if (p.live && nz) p.live[s_gid[lane]] = 1;
+        }
+        for (int e = lane; e < cnt * FB; e += 64) {
+            const int j = e / FB, c = e % FB;
+            p.frows[(size_t)s_row[j] * FB + c] = s_red[j][6 + c];
+        }
+        wave_lds_sync();  // the next batch overwrites the staged records, rows and sums
+    }
+}
+
+void launch_feat_bwd(hipStream_t s, const FeatBwdParams &p0) {
+    if (p0.num_tiles <= 0) return;
+    FeatBwdParams p = p0;
+    p.strip_exact = tuning("strip_exact", 1);
+    const dim3 grid((uint32_t)p.num_tiles), block(64);
+    if (tuning("guard", 0)) {  // as the forward ran
+        if (feat_block(p.C) == 8) feat_bwd_kernel<8, true><<<grid, block, 0, s>>>(p);
+        else feat_bwd_kernel<16, true><<<grid, block, 0, s>>>(p);
+        return;
+    }
+    if (feat_block(p.C) == 8) feat_bwd_kernel<8><<<grid, block, 0, s>>>(p);
+    else feat_bwd_kernel<16><<<grid, block, 0, s>>>(p);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Gaussians with more than BIG_GAUSSIAN_TILES instances: one workgroup sums the block's feature rows of all their
+// instances (256 / FB instance lanes x FB channels, fixed stride order, then the lanes in order) into bigsum[slot],
+// which the gather reads instead of walking the rows.  The count comes from the host, or, when only an upper bound is
+// known there, from the device word the preprocess left (big_reduce_kernel's PERSIST form).
+// ------------------------------------------------------------------------------------------------
+template <int FB>
+__global__ __launch_bounds__(256) void feat_big_reduce_kernel(FeatGatherParams p) {
+    constexpr int KL = 256 / FB;
+    __shared__ float s_p[KL][FB];
+    const int c = threadIdx.x % FB, kl = threadIdx.x / FB;
+    const uint32_t nb = p.nbig_dev ? *p.nbig_dev : p.nbig;
+    for (uint32_t bi = blockIdx.x; bi < nb; bi += gridDim.x) {  // workgroup-uniform
+        const uint32_t gidx = p.big_list[bi];
+        const uint32_t start = p.inst_start[gidx], cnt = p.tiles[gidx];
+        float acc = 0.f;
+        for (uint32_t k = (uint32_t)kl; k < cnt; k += KL)
+            if (p.inv[start + k] != INV_NONE) acc += p.frows[(size_t)(start + k) * FB + c];
+        s_p[kl][c] = acc;
+        __syncthreads();
+        if (threadIdx.x < FB) {
+            float tot = 0.f;
+            for (int q = 0; q < KL; q++) tot += s_p[q][threadIdx.x];
+            p.bigsum[(size_t)bi * FB + threadIdx.x] = tot;
+        }
+        __syncthreads();  // s_p is rewritten by the next big Gaussian
+    }
+}
+
+// Feature gather: dL_dfeatures[g][c0 .. c0 + FB) = the Gaussian's feature rows summed in instance order, under the
+// tests of launch_abs_gather (a positive radius, the live flag when the composite marked them, inv != INV_NONE per
+// instance); a big Gaussian takes feat_big_reduce_kernel's sum.  One thread per (Gaussian, channel): a Gaussian's FB
+// threads read one 32- or 64-B row segment together.  Every element is written (exact zeros for a Gaussian that is
+// culled or that no pixel takes); 4-B stores, the output need only be 4-B aligned.
+template <int FB>
+__global__ __launch_bounds__(256) void feat_gather_kernel(FeatGatherParams p) {
+    const int c = threadIdx.x % FB;
+    const int64_t g = (int64_t)blockIdx.x * (256 / FB) + threadIdx.x / FB;
+    if (g >= p.P || p.c0 + c >= p.C) return;
+    float acc = 0.f;
+    if (p.radii[g] > 0 && (!p.live || !*p.live_valid || p.live[g])) {
+        const uint32_t start = p.inst_start[g], cnt = p.tiles[g];
+        if (cnt > BIG_GAUSSIAN_TILES) {
+            acc = p.bigsum[(size_t)p.big_slot[g] * FB + c];
+        } else {
+            // four inv words, then four rows, in flight together (abs_gather_kernel's form); added in instance order
+            for (uint32_t k0 = 0; k0 < cnt; k0 += 4) {
+                uint32_t iv[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) iv[j] = p.inv[start + min(k0 + j, cnt - 1)];  // unconditional (clamped)
+                float rw[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const bool use = k0 + j < cnt && iv[j] != INV_NONE;
+                    rw[j] = use ? p.frows[(size_t)(start + k0 + j) * FB + c] : 0.f;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc += rw[j];
+            }
+        }
+    }
+    p.out[(size_t)g * p.C + (p.c0 + c)] = acc;
+}
+
+void launch_feat_gather(hipStream_t s, const FeatGatherParams &p) {
+    if (p.P <= 0) return;
+    const uint32_t nbig_launch = p.nbig_dev ? std::min(p.nbig, 2048u) : p.nbig;
+    if (feat_block(p.C) == 8) {
+        if (nbig_launch) feat_big_reduce_kernel<8><<<nbig_launch, 256, 0, s>>>(p);
+        feat_gather_kernel<8><<<div_up((uint32_t)p.P, 256u / 8u), 256, 0, s>>>(p);
+    } else {
+        if (nbig_launch) feat_big_reduce_kernel<16><<<nbig_launch, 256, 0, s>>>(p);
+        feat_gather_kernel<16><<<div_up((uint32_t)p.P, 256u / 16u), 256, 0, s>>>(p);
+    }
+}
+
+}  // namespace gsr

@@ -295,6 +295,51 @@ void launch_abs_gather(hipStream_t s, const AbsGatherParams &p);
 size_t camera_partials_bytes(int64_t n);
 void launch_camera_reduce(hipStream_t s, const PreprocessBwdParams &p, float *dview, float *dproj, float *dcampos);
 
+// ---- per-Gaussian feature channels (gsr_features.hip) ----
+constexpr int FEAT_MAX_C = 64;
+int feat_block(int C);  // channels one launch carries: 8 (C <= 8) or 16; the walks repeat per block
+// out (C,H,W) = sum_i alpha_i T_i features[i][c], the colour forward's weights replayed from its recorded state
+struct FeatFwdParams {
+    int W, H, gx, gy, num_tiles, C;
+    const uint2 *ranges;
+    const uint32_t *point_list, *n_contrib, *tile_last;
+    const GRec *rec;
+    const float *features;  // (P,C), 4-B aligned
+    float *out;
+    int strip_exact;  // as RenderFwdParams::strip_exact (set by launch)
+};
+void launch_feat_fwd(hipStream_t s, const FeatFwdParams &p);
+// One channel block [c0, c0 + feat_block(C)) of the feature compositing backward, after launch_render_bwd and before
+// launch_big_reduce: adds the block's geometry terms into rows[..][0..5] and writes frows (R x feat_block(C) floats by
+// expansion index: sum_pix w_i(pix) dL_dF_c(pix))
+struct FeatBwdParams {
+    int W, H, gx, gy, num_tiles, C, c0;
+    const uint2 *ranges;
+    const uint32_t *point_list, *n_contrib, *tile_last, *tile_loaded, *sorted_u;
+    const GRec *rec;
+    const float *final_T, *features, *dL_dF;  // dL_dF (C,H,W)
+    float *rows, *frows;
+    uint8_t *live;  // as RenderBwdParams::live, or null
+    int strip_exact;  // (set by launch)
+};
+void launch_feat_bwd(hipStream_t s, const FeatBwdParams &p);
+// out[g][c0 .. c0 + feat_block(C)) of dL_dfeatures (P,C): the Gaussian's frows summed in instance order under
+// launch_abs_gather's tests; Gaussians with more than BIG_GAUSSIAN_TILES instances through bigsum (nbig x
+// feat_block(C) floats), which the launch fills first
+struct FeatGatherParams {
+    int P, C, c0;
+    const int *radii;
+    const uint32_t *tiles, *inst_start, *big_slot, *big_list, *inv;
+    const uint8_t *live;
+    const uint32_t *live_valid;
+    const float *frows;
+    float *bigsum;
+    uint32_t nbig;             // big Gaussians, or an upper bound with nbig_dev the device's count
+    const uint32_t *nbig_dev;  // or null
+    float *out;
+};
+void launch_feat_gather(hipStream_t s, const FeatGatherParams &p);
+
 // ---- multi-view SH gradient (gsr_views.hip) ----
 void launch_sh_backward_views(hipStream_t s, int P, int D, int M, int V, int chunk_len, const float *means3D,
                               const float *campos, const float *dcolors_sh, float *dsh);

@@ -190,6 +190,9 @@ class ViewGradReducer:
     With chunks == 1, ``backward_raw(..., out=red.backward_out(), ...)`` followed by ``red.reduce(means3D, campos)``
     is the same exchange without overlap.
 
+    Feature channels (``forward_raw(..., features=...)``) are not exchanged: ``backward_chunked`` raises
+    NotImplementedError for a forward state that carries features, and the exchange has no block for their gradient.
+
     mode="sharded" (and mode="auto" when the cost model picks it): ``grads`` and ``sh_views_gradient`` cover only this
     rank's shard ``self.shard`` = [g0, g1); the caller steps those rows of its parameters (padded to
     ``padded_rows()``) and calls ``gather_shards(params)``; ``reduce`` takes this view's campos.

@@ -16,6 +16,9 @@ return alpha (1,H,W) = 1 - final transmittance, and settings.bg may be a (3,H,W)
 it requires grad (gsr_forward_ext / gsr_backward_ext); without either the call is upstream's.
 GaussianRasterizer(settings, absgrad=True) / rasterize_gaussians(..., absgrad=True) set means2D.absgrad (P,3) in the
 backward, as gsplat does: the absolute screen-space gradient of AbsGS for densification (gsr_backward_abs).
+rasterizer(..., features=f) / rasterize_gaussians(..., features=f) with f (P,C), 1 <= C <= 64, also return the feature
+image (C,H,W) = sum_i alpha_i T_i f[i] (no background) as the last output, differentiable with respect to f and,
+through alpha, to everything the colour is (gsr_forward_features / gsr_backward_features).
 Every computation runs in the HIP kernels on the tensors' device; the scratch state the backward needs
 (geometry/binning/image buffers) lives in uint8 tensors saved on the autograd context.
 """
@@ -125,6 +128,7 @@ class ForwardState(NamedTuple):
     num_rendered: int
     num_big: int
     M: int
+    features: Optional[torch.Tensor] = None  # the prepared (P,C) feature channels, when the forward was given any
 
 
 def _background(bg, H: int, W: int) -> bool:
@@ -136,14 +140,32 @@ def _background(bg, H: int, W: int) -> bool:
     raise RuntimeError(f"bg must have shape (3,) or (3, {H}, {W}), got {None if bg is None else tuple(bg.shape)}")
 
 
+def _features(features, P: int, device):
+    """The feature channels as a contiguous float32 (P,C) tensor on the device, 1 <= C <= 64; RuntimeError otherwise."""
+    if not torch.is_tensor(features) or features.ndim != 2 or features.shape[0] != P:
+        raise RuntimeError(f"features must have shape ({P}, C), got "
+                           f"{tuple(features.shape) if torch.is_tensor(features) else type(features).__name__}")
+    C = int(features.shape[1])
+    if not 1 <= C <= _native.FEATURES_MAX_C:
+        raise RuntimeError(f"features must have between 1 and {_native.FEATURES_MAX_C} channels, got {C}")
+    if features.dtype != torch.float32:
+        raise RuntimeError(f"features must be float32 (got {features.dtype})")
+    if features.device != device:
+        features = features.to(device)
+    return features.contiguous()
+
+
 def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                return_alpha=False):
+                return_alpha=False, features=None):
     """One call of gsr_forward.  Returns (color (3,H,W), radii (P,), invdepth (1,H,W), ForwardState).
     raster_settings.bg is the (3,) background or a (3,H,W) image, one background per pixel.  return_alpha=True returns
     (color, radii, invdepth, alpha (1,H,W), ForwardState), alpha = 1 - the transmittance left behind the pixel's last
     contributor (0 where no Gaussian reaches).  Either goes through gsr_forward_ext; the plain call is gsr_forward.
     With P == 0 the two differ in colour: the plain call returns zeros (upstream's early return), the ext call what the
-    composite writes where no Gaussian reaches, the background; every P > 0 colour is bitwise the same in both."""
+    composite writes where no Gaussian reaches, the background; every P > 0 colour is bitwise the same in both.
+    features (P,C), 1 <= C <= 64: the feature image (C,H,W) = sum_i alpha_i T_i features[i], with the colour's weights
+    and no background, is returned after alpha and before the state, which keeps the prepared features for the
+    backward (gsr_forward_features).  Colour, radii, invdepth and alpha are bitwise those of the call without."""
     lib = _native.load()
     device = means3D.device
     if device.type != "cuda":
@@ -166,6 +188,7 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
     proj = _prep(rs.projmatrix, device, "projmatrix")
     campos = _prep(rs.campos, device, "campos")
     M = 0 if sh_c is None else (sh_c.shape[1] if sh_c.ndim == 3 else sh_c.shape[1] // 3)
+    feat_c = None if features is None else _features(features, P, device)
 
     # fully written by the library (render_fwd writes every pixel, preprocess every radius; P == 0 clears)
     color = torch.empty(3, H, W, dtype=torch.float32, device=device)
@@ -175,6 +198,10 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
     ext = None
     if bg_image or return_alpha:
         ext = _native.CompositeExt(background_image=_ptr(bg) if bg_image else None, out_alpha=_ptr(alpha))
+    feat_image = feat = None
+    if feat_c is not None:
+        feat_image = torch.empty(feat_c.shape[1], H, W, dtype=torch.float32, device=device)
+        feat = _native.FeaturesExt(C=int(feat_c.shape[1]), features=_ptr(feat_c), out_features=feat_image.data_ptr())
     bufs = _Buffers(device)
     a = _native.ForwardArgs(
         P=P, D=int(rs.sh_degree), M=M, W=W, H=H, background=None if bg_image else _ptr(bg), means3D=_ptr(means3D_c),
@@ -186,7 +213,11 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
         out_invdepth=invdepth.data_ptr(), radii=radii.data_ptr())
     num_rendered = ctypes.c_int64(0)
     with torch.cuda.device(device):  # the library also switches to its stream's device (gsr_api.hip)
-        if ext is None:
+        if feat is not None:
+            rc = lib.gsr_forward_features(ctypes.byref(a), None if ext is None else ctypes.byref(ext),
+                                          ctypes.byref(feat), bufs.callback, None, _stream_handle(device),
+                                          ctypes.byref(num_rendered))
+        elif ext is None:
             rc = lib.gsr_forward(ctypes.byref(a), bufs.callback, None, _stream_handle(device),
                                  ctypes.byref(num_rendered))
         else:
@@ -196,10 +227,9 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
     _native.check(rc, "rasterize_gaussians")
     state = ForwardState(means3D_c, sh_c, col_c, op_c, sc_c, rot_c, cov_c, radii, bg, view, proj, campos,
                          bufs.get(_native.GSR_BUF_GEOM), bufs.get(_native.GSR_BUF_BINNING),
-                         bufs.get(_native.GSR_BUF_IMAGE), int(num_rendered.value), int(a.num_big_out), M)
-    if return_alpha:
-        return color, radii, invdepth, alpha, state
-    return color, radii, invdepth, state
+                         bufs.get(_native.GSR_BUF_IMAGE), int(num_rendered.value), int(a.num_big_out), M, feat_c)
+    res = (color, radii, invdepth) + ((alpha,) if return_alpha else ()) + ((feat_image,) if feat is not None else ())
+    return (*res, state)
 
 
 def _alpha_grad(grad_out_alpha, H: int, W: int):
@@ -213,7 +243,7 @@ def _alpha_grad(grad_out_alpha, H: int, W: int):
 
 def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_depth=None, out=None,
                  compact_sh=False, accumulate_stats=False, camera_grads=False, grad_out_alpha=None,
-                 background_grad=False, absgrad=False, abs_stats=False):
+                 background_grad=False, absgrad=False, abs_stats=False, grad_out_features=None):
     """One call of gsr_backward.  Returns a dict of gradients (means3D, means2D, shs, colors_precomp,
     opacities, scales, rotations, cov3D_precomp); entries are None where the input was absent.
     `out` may supply preallocated contiguous float32 destinations (e.g. views into one flat buffer that is
@@ -239,7 +269,13 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     other gradient keeps its bits.  `out` may supply it as out["means2D_abs"] (which also asks for it).
     abs_stats=True (needs out["densify_stats"]; implies absgrad) forms densify_stats[:, 0] from that vector,
     sqrt(x * x + y * y) with every operation rounded once, instead of from the signed gradient.  The call is then
-    gsr_backward_abs."""
+    gsr_backward_abs.
+    A state that carries features (forward_raw(..., features=f)) adds "features" (P,C), the gradient of f; `out` may
+    supply it as out["features"].  grad_out_features (C,H,W) is the upstream gradient of the feature image: through
+    alpha it also enters every other gradient of the call, which then is the joint gradient of colour, inverse depth,
+    alpha and features.  With grad_out_features=None "features" is zeros and every other gradient has the bits of the
+    call without features.  The call is then gsr_backward_features; absgrad / abs_stats with it raise
+    NotImplementedError (the absolute sums of a joint call are not built)."""
     if abs_stats and "densify_stats" not in (out or {}):
         raise RuntimeError("abs_stats=True needs out['densify_stats']")
     lib = _native.load()
@@ -287,6 +323,19 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     dproj = dst("projmatrix", 4, 4) if camera_grads else None
     dcampos = dst("campos", 3) if camera_grads else None
     dbg = dst("bg", *st.bg.shape) if (background_grad or "bg" in out) else None
+    feat = dfeat = None
+    if st.features is not None:
+        C = int(st.features.shape[1])
+        if grad_out_features is not None:
+            if tuple(grad_out_features.shape) != (C, H, W):
+                raise RuntimeError(f"grad_out_features must have shape ({C}, {H}, {W}), got "
+                                   f"{tuple(grad_out_features.shape)}")
+            grad_out_features = grad_out_features.to(torch.float32).contiguous()
+        dfeat = dst("features", P, C)
+        feat = _native.FeaturesExt(C=C, features=_ptr(st.features), dL_dout_features=_ptr(grad_out_features),
+                                   dL_dfeatures=_ptr(dfeat))
+    elif grad_out_features is not None:
+        raise RuntimeError("grad_out_features needs a state from forward_raw(..., features=...)")
     ext = None
     if bg_image or grad_out_alpha is not None or dbg is not None:
         ext = _native.CompositeExt(background_image=_ptr(st.bg) if bg_image else None, dL_dalpha=_ptr(grad_out_alpha),
@@ -310,7 +359,14 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
         campos_rows=cam_rows, campos_rank=cam_rank, campos_nrows=cam_n,
         dL_dviewmatrix=_ptr(dview), dL_dprojmatrix=_ptr(dproj), dL_dcampos=_ptr(dcampos))
     with torch.cuda.device(device):
-        if dabs is not None:
+        if feat is not None:
+            ab = None
+            if dabs is not None:  # (refused by the library: GSR_ERR_UNSUPPORTED -> NotImplementedError)
+                ab = _native.AbsgradExt(dL_dmeans2D_abs=dabs.data_ptr(), densify_abs=int(bool(abs_stats) and P > 0))
+            rc = lib.gsr_backward_features(ctypes.byref(a), None if ext is None else ctypes.byref(ext),
+                                           None if ab is None else ctypes.byref(ab), ctypes.byref(feat),
+                                           bufs.callback, None, _stream_handle(device))
+        elif dabs is not None:
             # (P == 0: the pointer of an empty tensor is passed as NULL and the library writes nothing)
             ab = _native.AbsgradExt(dL_dmeans2D_abs=_ptr(dabs), densify_abs=int(bool(abs_stats) and P > 0))
             rc = lib.gsr_backward_abs(ctypes.byref(a), None if ext is None else ctypes.byref(ext), ctypes.byref(ab),
@@ -326,6 +382,8 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
         camera["bg"] = dbg
     if dabs is not None:
         camera["means2D_abs"] = dabs
+    if dfeat is not None:
+        camera["features"] = dfeat
     return dict(
         **camera,
         means3D=dmeans3D, means2D=dmeans2D,
@@ -356,10 +414,14 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
     (backward_raw's "bg").
     A chunk's out may hold means2D_abs ((g_end - g_begin), 2), backward_raw's "means2D_abs" for those Gaussians: then
     every chunk must, since the compositing call produces the rows they are summed from.  abs_stats=True forms each
-    chunk's densify_stats[:, 0] from it (every chunk then needs both)."""
+    chunk's densify_stats[:, 0] from it (every chunk then needs both).
+    A state that carries features raises NotImplementedError: the split backward of feature channels is not built."""
     lib = _native.load()
     rs = raster_settings
     st = state
+    if st.features is not None:
+        raise NotImplementedError("backward_chunked: a forward state with features needs backward_raw (the split "
+                                  "backward of feature channels is not built)")
     device = st.radii.device  # (as backward_raw: a scene without Gaussians keeps no means3D)
     P, M = st.radii.shape[0], st.M
     H, W = int(rs.image_height), int(rs.image_width)
@@ -506,22 +568,62 @@ class _RasterizeGaussians(torch.autograd.Function):
         if ctx.absgrad_of is not None:  # (P,3) with z = 0, so code that takes [:, :2] of means2D.grad works on it
             m2a = g["means2D_abs"]
             ctx.absgrad_of.absgrad = torch.cat([m2a, m2a.new_zeros(m2a.shape[0], 1)], dim=1)
-        camera = tuple(g[name].reshape(shape).to(dev) if wanted else None for name, (shape, dev), wanted in
-                       zip(("viewmatrix", "projmatrix", "campos"), ctx.camera, need[12:]))
-        camera = (None, None, g["bg"].reshape(ctx.bg[0]).to(ctx.bg[1]) if need[11] else None) + camera
-        return (g["means3D"] if need[0] else None,
-                g["means2D"] if need[1] else None,
-                g["shs"] if need[2] else None,
-                g["colors_precomp"] if need[3] else None,
-                g["opacities"] if need[4] else None,
-                g["scales"] if need[5] else None,
-                g["rotations"] if need[6] else None,
-                g["cov3D_precomp"] if need[7] else None,
-                None, *camera)
+        return _input_grads(ctx, g, need)
+
+
+def _input_grads(ctx, g, need):
+    """backward_raw's result as the gradients of _RasterizeGaussians.forward's inputs (need: their needs_input_grad)."""
+    camera = tuple(g[name].reshape(shape).to(dev) if wanted else None for name, (shape, dev), wanted in
+                   zip(("viewmatrix", "projmatrix", "campos"), ctx.camera, need[12:]))
+    camera = (None, None, g["bg"].reshape(ctx.bg[0]).to(ctx.bg[1]) if need[11] else None) + camera
+    return (g["means3D"] if need[0] else None,
+            g["means2D"] if need[1] else None,
+            g["shs"] if need[2] else None,
+            g["colors_precomp"] if need[3] else None,
+            g["opacities"] if need[4] else None,
+            g["scales"] if need[5] else None,
+            g["rotations"] if need[6] else None,
+            g["cov3D_precomp"] if need[7] else None,
+            None, *camera)
+
+
+class _RasterizeGaussiansFeatures(torch.autograd.Function):
+    """_RasterizeGaussians with feature channels, a function of its own so that the call without features stays what
+    it is: features is the first input, the feature image (C,H,W) the last output."""
+
+    @staticmethod
+    def forward(ctx, features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings, return_alpha=False, bg=None, *camera):
+        res = forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                          return_alpha=return_alpha, features=features)
+        st = res[-1]
+        ctx.raster_settings = raster_settings
+        ctx.return_alpha = bool(return_alpha)
+        ctx.bg = None if bg is None else (tuple(bg.shape), bg.device)
+        ctx.camera = [(tuple(t.shape), t.device) for t in camera]
+        ctx.meta = (st.num_rendered, st.num_big, st.M)
+        ctx.present = tuple(t is not None for t in st)
+        empty = torch.empty(0, device=means3D.device)
+        ctx.save_for_backward(*[(t if t is not None else empty) for t in st[:15]], st.features)
+        ctx.set_materialize_grads(False)
+        return res[:-1]  # (color, radii, invdepth[, alpha], feature_image)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, *rest):
+        grad_out_alpha, grad_out_features = rest if ctx.return_alpha else (None, rest[0])
+        saved = ctx.saved_tensors
+        tensors = [t if present else None for t, present in zip(saved[:15], ctx.present[:15])]
+        st = ForwardState(*tensors, *ctx.meta, saved[15])
+        need = ctx.needs_input_grad[1:]  # as _RasterizeGaussians' inputs, but for absgrad (index 10, a flag)
+        need = need[:10] + (False,) + need[10:]
+        g = backward_raw(st, ctx.raster_settings, grad_out_color, grad_out_depth, camera_grads=any(need[12:]),
+                         grad_out_alpha=grad_out_alpha, background_grad=need[11], grad_out_features=grad_out_features)
+        grads = _input_grads(ctx, g, need)
+        return (g["features"] if ctx.needs_input_grad[0] else None, *grads[:10], *grads[11:])
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, return_alpha=False, absgrad=False):
+                        raster_settings, return_alpha=False, absgrad=False, features=None):
     """Differentiable with respect to the Gaussians' tensors and, where raster_settings.viewmatrix, .projmatrix or
     .campos requires grad, to those three as independent inputs (projmatrix being the full view-projection product:
     a caller optimising a pose builds projmatrix and campos from its view matrix in torch, which chains the three).
@@ -532,13 +634,23 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     upstream, this one the background (forward_raw).
     absgrad=True: the backward also sets means2D.absgrad (P,3) = (sum over the Gaussian's pixels of |the pixel's
     contribution to means2D.grad[:, :2]|, 0), the AbsGS densification criterion, as gsplat's absgrad does; it is
-    assigned (not accumulated) by every backward, and means2D.grad is what it is without."""
+    assigned (not accumulated) by every backward, and means2D.grad is what it is without.
+    features (P,C), 1 <= C <= 64: the call returns (color, radii, invdepth[, alpha], feature_image (C,H,W)) with
+    feature_image = sum_i alpha_i T_i features[i] -- the colour's weights, no background.  It takes part in autograd:
+    features.grad is populated, and a loss on it reaches means3D, opacities, scales, rotations and the camera through
+    alpha.  With absgrad=True it raises NotImplementedError (the absolute sums of a joint call are not built)."""
+    if features is not None and absgrad:
+        raise NotImplementedError("features with absgrad=True are not built yet")
     rs = raster_settings
     camera = (rs.viewmatrix, rs.projmatrix, rs.campos)
     if not (torch.is_grad_enabled() and all(torch.is_tensor(t) for t in camera)
             and any(t.requires_grad for t in camera)):
         camera = ()  # the call as it is without camera gradients
     bg = rs.bg if (torch.is_grad_enabled() and torch.is_tensor(rs.bg) and rs.bg.requires_grad) else None
+    if features is not None:
+        return _RasterizeGaussiansFeatures.apply(features, means3D, means2D, sh, colors_precomp, opacities, scales,
+                                                 rotations, cov3Ds_precomp, raster_settings, bool(return_alpha), bg,
+                                                 *camera)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, bool(return_alpha), bool(absgrad), bg, *camera)
 
@@ -604,12 +716,16 @@ class GaussianRasterizer(nn.Module):
             return mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, features=None):
         rs = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        if features is not None:  # (color, radii, invdepth[, alpha], feature_image (C,H,W)): rasterize_gaussians
+            return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                       cov3D_precomp, rs, return_alpha=self.return_alpha, absgrad=self.absgrad,
+                                       features=features)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs, return_alpha=self.return_alpha, absgrad=self.absgrad)

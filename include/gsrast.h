@@ -224,6 +224,49 @@ typedef struct gsr_absgrad_ext {
 int gsr_backward_abs(const gsr_backward_args *args, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
                      gsr_alloc_fn alloc, void *alloc_ctx, void *stream);
 
+/* Per-Gaussian feature channels (the arbitrary-channel `colors` of gsplat): a third side struct, versioned by its own
+ * size like the two above, so gsr_forward_args, gsr_backward_args, gsr_composite_ext, gsr_absgrad_ext and
+ * GSR_ABI_VERSION stay as they are.  features (P,C), 1 <= C <= 64, any fp32 values (semantic or language features,
+ * normals, view-space depth, ids, ...), are composited with the weights of the colour render:
+ *   out_features_c(pix) = sum_i w_i(pix) features[i][c],  w_i = alpha_i T_i, front to back like the colour, with NO
+ *     background term (fully written; zeros where no Gaussian reaches).  The weights are replayed from the state the
+ *     colour composite recorded, with its arithmetic: the same values passed as colours (background 0) give the same bits.
+ *   backward: dL_dfeatures[i][c] = sum_pix w_i(pix) dL_dout_features_c(pix) (fully written; exactly 0 for a Gaussian
+ *     that is culled or that no pixel takes), and, through alpha, the features' share of EVERY other gradient of the
+ *     call: their geometry terms are added into the per-instance gradient rows before the per-Gaussian stage, so
+ *     dL_dmeans2D / dL_dopacity / dL_dmeans3D / dL_dcov3D / dL_dscales / dL_drotations, densify_stats and the camera
+ *     gradients come out as the joint gradient of colour, inverse depth, alpha and features.  Summed in a fixed order
+ *     (no float atomics): two calls give the same bits.
+ *   dL_dout_features == NULL: none of the feature work is launched, dL_dfeatures (if given) is written as zeros and
+ *     every other output keeps the bits it has without the struct.
+ * The pointers need only be 4-B aligned (a row of (P,C) with odd C is not 16-B aligned).
+ * With P = 0 or nothing rendered out_features is zeros and dL_dfeatures is written as zeros (nothing for P = 0).
+ * Scratch: the backward asks for a GSR_BUF_BWD_SCRATCH buffer of gsr_bwd_scratch_bytes_features(R, num_big, C) bytes:
+ * gsr_bwd_scratch_bytes plus the feature rows of ONE channel block (R x 8 floats for C <= 8, else R x 16 floats; the
+ * blocks of 8 / 16 channels are walked and gathered one after the other and reuse them) plus one such row per big
+ * Gaussian -- 64 B per instance at most, whatever C is, instead of 4 C.
+ * GSR_ERR_ARG, before any device work or allocation: C < 1 or C > 64, a missing features (P > 0) / out_features
+ * pointer, struct_size ending before the first pointer field.
+ * GSR_ERR_UNSUPPORTED, before any device work -- not yet built:
+ *   features together with gsr_absgrad_ext.dL_dmeans2D_abs (|.| is not linear: the absolute sums of a joint call
+ *     cannot be formed by adding the features' terms);
+ *   features with stages != GSR_BWD_ALL (the split backward).
+ * Under the "guard" tuning knob the feature kernels take the guard's decision path (guard_alpha_pass) like the colour
+ * kernels: supported, provided forward and backward run with the same knob, as for the colour. */
+typedef struct gsr_features_ext {
+    size_t struct_size;               /* sizeof as the caller was built; fields past it are read as NULL */
+    int C;                            /* channels, 1..64 */
+    const float *features;            /* (P,C) */
+    float *out_features;              /* forward: (C,H,W), fully written */
+    const float *dL_dout_features;    /* backward: (C,H,W) or NULL */
+    float *dL_dfeatures;              /* backward: (P,C), fully written, or NULL */
+} gsr_features_ext;
+/* gsr_forward_ext / gsr_backward_abs are these with feat = NULL. */
+int gsr_forward_features(gsr_forward_args *args, const gsr_composite_ext *ext, const gsr_features_ext *feat,
+                         gsr_alloc_fn alloc, void *alloc_ctx, void *stream, int64_t *num_rendered);
+int gsr_backward_features(const gsr_backward_args *args, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
+                          const gsr_features_ext *feat, gsr_alloc_fn alloc, void *alloc_ctx, void *stream);
+
 /* Multi-view SH gradient from compact per-view factors (no counterpart in the reference, whose batch size is
  * one view: gs_lightning_module.py:139-141).  dL_dsh[g] = sum_v basis(normalize(means3D[g] - campos[v]))
  * (x) dL_dcolors_sh[v][g], i.e. the sum over views of gsr_backward's dL_dsh -- what an all-reduce of dL_dsh
@@ -386,6 +429,9 @@ size_t gsr_binning_buffer_bytes(int64_t R, int W, int H);
 size_t gsr_image_buffer_bytes(int W, int H);
 size_t gsr_bwd_scratch_bytes(int64_t R, int64_t num_big);
 size_t gsr_bwd_scratch_bytes_abs(int64_t R, int64_t num_big); /* with gsr_absgrad_ext.dL_dmeans2D_abs */
+/* with gsr_features_ext.dL_dout_features: gsr_bwd_scratch_bytes + align256(max(R,1) * B * 4) + align256(max(num_big,1) *
+ * B * 4), B = 8 for C <= 8 and 16 above (one channel block's rows; 0 for C outside 1..64) */
+size_t gsr_bwd_scratch_bytes_features(int64_t R, int64_t num_big, int C);
 
 /* Byte offsets of the internal arrays inside the three forward buffers (host arithmetic only).  Used by
  * the parity tests to compare the integer binning state (sorted instance list, tile ranges,
