@@ -283,6 +283,36 @@ def load(path: str | None = None):
     return lib
 
 
+def _ref(struct):
+    return None if struct is None else ctypes.byref(struct)
+
+
+def call_forward(lib, args, ext, feat, cb, stream, num_rendered) -> int:
+    """The forward through the narrowest entry point whose extra arguments are all given: gsr_forward, gsr_forward_ext
+    (ext: CompositeExt) or gsr_forward_features (feat: FeaturesExt, ext given or None).  Which one is behaviour: at
+    P == 0 the plain call returns zeros where the ext call returns the background.  The entry point is looked up on
+    `lib` here, at call time, so a patched attribute is what runs."""
+    a, n = ctypes.byref(args), ctypes.byref(num_rendered)
+    if feat is not None:
+        return lib.gsr_forward_features(a, _ref(ext), ctypes.byref(feat), cb, None, stream, n)
+    if ext is not None:
+        return lib.gsr_forward_ext(a, ctypes.byref(ext), cb, None, stream, n)
+    return lib.gsr_forward(a, cb, None, stream, n)
+
+
+def call_backward(lib, args, ext, absgrad, feat, cb, stream) -> int:
+    """The backward likewise: gsr_backward, gsr_backward_ext (ext), gsr_backward_abs (absgrad: AbsgradExt, ext given or
+    None) or gsr_backward_features (feat: FeaturesExt, ext and absgrad given or None)."""
+    a = ctypes.byref(args)
+    if feat is not None:
+        return lib.gsr_backward_features(a, _ref(ext), _ref(absgrad), ctypes.byref(feat), cb, None, stream)
+    if absgrad is not None:
+        return lib.gsr_backward_abs(a, _ref(ext), ctypes.byref(absgrad), cb, None, stream)
+    if ext is not None:
+        return lib.gsr_backward_ext(a, ctypes.byref(ext), cb, None, stream)
+    return lib.gsr_backward(a, cb, None, stream)
+
+
 def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().gsr_last_error().decode(errors="replace")

@@ -364,8 +364,22 @@ int check_common(int P, int D, int M, int W, int H, const float *means3D, const 
     return GSR_OK;
 }
 
-// gsr_composite_ext as the library reads it: the fields the caller's struct_size covers, NULL past it (and all NULL
-// without the struct: gsr_forward / gsr_backward)
+// A caller's versioned struct (first member struct_size; fields are only ever appended) as the library reads it: the
+// caller's min(struct_size, sizeof(T)) bytes over zeros.  A member the caller covers only in part is not there (get: 0).
+template <typename T>
+struct VersionedIn {
+    T full{};
+    size_t size;
+    explicit VersionedIn(const T *x) : size(x->struct_size) { memcpy(&full, x, std::min(size, sizeof(T))); }
+    template <typename M>
+    bool covers(M T::*m) const {
+        return (size_t)(reinterpret_cast<const char *>(&(full.*m)) - reinterpret_cast<const char *>(&full)) + sizeof(M) <= size;
+    }
+    template <typename M>
+    M get(M T::*m) const { return covers(m) ? full.*m : M{}; }
+};
+
+// gsr_composite_ext as the library reads it (all NULL without the struct: gsr_forward / gsr_backward)
 struct CompositeExt {
     bool given = false;
     const float *background_image = nullptr;
@@ -375,39 +389,33 @@ struct CompositeExt {
 };
 int read_composite_ext(const gsr_composite_ext *ext, const float *background, CompositeExt &e) {
     if (!ext) return GSR_OK;
-    if (ext->struct_size < offsetof(gsr_composite_ext, background_image) + sizeof(ext->background_image))
+    const VersionedIn<gsr_composite_ext> in(ext);
+    if (!in.covers(&gsr_composite_ext::background_image))
         return fail(GSR_ERR_ARG, "gsr_composite_ext: struct_size ends before the first pointer field");
-    gsr_composite_ext full{};
-    memcpy(&full, ext, std::min(ext->struct_size, sizeof(full)));
-    // a field the caller's struct covers only in part is not there
-    auto has = [&](size_t off) { return off + sizeof(void *) <= ext->struct_size; };
     e.given = true;
-    e.background_image = full.background_image;
-    if (has(offsetof(gsr_composite_ext, out_alpha))) e.out_alpha = full.out_alpha;
-    if (has(offsetof(gsr_composite_ext, dL_dalpha))) e.dL_dalpha = full.dL_dalpha;
-    if (has(offsetof(gsr_composite_ext, dL_dbackground))) e.dL_dbackground = full.dL_dbackground;
-    if (has(offsetof(gsr_composite_ext, dL_dbackground_image))) e.dL_dbackground_image = full.dL_dbackground_image;
+    e.background_image = in.get(&gsr_composite_ext::background_image);
+    e.out_alpha = in.get(&gsr_composite_ext::out_alpha);
+    e.dL_dalpha = in.get(&gsr_composite_ext::dL_dalpha);
+    e.dL_dbackground = in.get(&gsr_composite_ext::dL_dbackground);
+    e.dL_dbackground_image = in.get(&gsr_composite_ext::dL_dbackground_image);
     if (!background && !e.background_image)
         return fail(GSR_ERR_ARG, "one of background and gsr_composite_ext.background_image is required");
     return GSR_OK;
 }
 
-// gsr_absgrad_ext as the library reads it: a field the caller's struct does not cover whole is NULL / 0
+// gsr_absgrad_ext as the library reads it
 struct AbsgradExt {
     float *dL_dmeans2D_abs = nullptr;
     int densify_abs = 0;
 };
 void read_absgrad_ext(const gsr_absgrad_ext *x, AbsgradExt &e) {
     if (!x) return;
-    gsr_absgrad_ext full{};
-    memcpy(&full, x, std::min(x->struct_size, sizeof(full)));
-    if (offsetof(gsr_absgrad_ext, dL_dmeans2D_abs) + sizeof(full.dL_dmeans2D_abs) <= x->struct_size)
-        e.dL_dmeans2D_abs = full.dL_dmeans2D_abs;
-    if (offsetof(gsr_absgrad_ext, densify_abs) + sizeof(full.densify_abs) <= x->struct_size)
-        e.densify_abs = full.densify_abs;
+    const VersionedIn<gsr_absgrad_ext> in(x);
+    e.dL_dmeans2D_abs = in.get(&gsr_absgrad_ext::dL_dmeans2D_abs);
+    e.densify_abs = in.get(&gsr_absgrad_ext::densify_abs);
 }
 
-// gsr_features_ext as the library reads it: a field the caller's struct does not cover whole is NULL
+// gsr_features_ext as the library reads it
 struct FeaturesExt {
     bool given = false;
     int C = 0;
@@ -419,17 +427,15 @@ struct FeaturesExt {
 // the checks both directions share: the struct's size, C and the features pointer
 int read_features_ext(const gsr_features_ext *x, int P, FeaturesExt &f) {
     if (!x) return GSR_OK;
-    if (x->struct_size < offsetof(gsr_features_ext, features) + sizeof(x->features))
+    const VersionedIn<gsr_features_ext> in(x);
+    if (!in.covers(&gsr_features_ext::features))
         return fail(GSR_ERR_ARG, "gsr_features_ext: struct_size ends before the first pointer field");
-    gsr_features_ext full{};
-    memcpy(&full, x, std::min(x->struct_size, sizeof(full)));
-    auto has = [&](size_t off) { return off + sizeof(void *) <= x->struct_size; };
     f.given = true;
-    f.C = full.C;
-    f.features = full.features;
-    if (has(offsetof(gsr_features_ext, out_features))) f.out_features = full.out_features;
-    if (has(offsetof(gsr_features_ext, dL_dout_features))) f.dL_dout_features = full.dL_dout_features;
-    if (has(offsetof(gsr_features_ext, dL_dfeatures))) f.dL_dfeatures = full.dL_dfeatures;
+    f.C = in.get(&gsr_features_ext::C);
+    f.features = in.get(&gsr_features_ext::features);
+    f.out_features = in.get(&gsr_features_ext::out_features);
+    f.dL_dout_features = in.get(&gsr_features_ext::dL_dout_features);
+    f.dL_dfeatures = in.get(&gsr_features_ext::dL_dfeatures);
     if (f.C < 1 || f.C > FEAT_MAX_C) return fail(GSR_ERR_ARG, "gsr_features_ext: C must be in [1, 64]");
     if (P > 0 && !f.features) return fail(GSR_ERR_ARG, "gsr_features_ext: features is required");
     return GSR_OK;
@@ -452,10 +458,14 @@ size_t gsr_image_buffer_bytes(int W, int H) {
     ImageState im;
     return carve_image(nullptr, W, H, im);
 }
-size_t gsr_bwd_scratch_bytes(int64_t R, int64_t num_big) { return bwd_scratch_bytes(R, num_big); }
-size_t gsr_bwd_scratch_bytes_abs(int64_t R, int64_t num_big) { return bwd_scratch_bytes_abs(R, num_big); }
+static size_t bwd_scratch_size(int64_t R, int64_t nbig, bool abs, int feat_block) {
+    BwdScratch sc;
+    return carve_bwd_scratch(nullptr, R, nbig, abs, feat_block, sc);
+}
+size_t gsr_bwd_scratch_bytes(int64_t R, int64_t num_big) { return bwd_scratch_size(R, num_big, false, 0); }
+size_t gsr_bwd_scratch_bytes_abs(int64_t R, int64_t num_big) { return bwd_scratch_size(R, num_big, true, 0); }
 size_t gsr_bwd_scratch_bytes_features(int64_t R, int64_t num_big, int C) {
-    return (C < 1 || C > FEAT_MAX_C) ? 0 : bwd_scratch_bytes_features(R, num_big, feat_block(C));
+    return (C < 1 || C > FEAT_MAX_C) ? 0 : bwd_scratch_size(R, num_big, false, feat_block(C));
 }
 
 void gsr_state_layout_query(int P, int64_t R, int W, int H, gsr_state_layout *caller) {
@@ -911,6 +921,255 @@ static int background_grads(const gsr_backward_args *a, const CompositeExt &e, c
     return GSR_OK;
 }
 
+// One backward call's state: what the argument checks read and derived, the carved buffers, and what one stage leaves
+// for the next.  Each stage below takes it whole.
+struct BwdCall {
+    const gsr_backward_args *a;
+    gsr_alloc_fn alloc;
+    void *alloc_ctx;
+    hipStream_t stream;
+    bool dbg;
+    CompositeExt e;
+    AbsgradExt ab;
+    FeaturesExt fx;
+    bool feat_bwd;   // the feature work of this call: only with an upstream gradient of the feature image
+    int64_t g0, g1;  // the Gaussians of the per-Gaussian stage
+    int gx, gy;
+    uint32_t T, R;
+    // num_big < 0: not known on the host (the upstream backward signature has no such argument, gsr_torch_ext): nbig
+    // is then the most there can be (each has > BIG_GAUSSIAN_TILES instances), which sizes the sums, and nbig_dev the
+    // count the preprocess left in the geometry buffer, which the reductions read; else nbig is exact, nbig_dev null
+    uint32_t nbig;
+    const uint32_t *nbig_dev;
+    GeomState g;
+    BinningState b;
+    ImageState im;
+    BwdScratch sc;
+    GatherSrc src;   // what every gather of this call tests (live: null with "bwd_live" 0, decided once)
+    bool prezeroed;  // the composite zero-filled the per-Gaussian outputs (zero_fill_plan), and did launch
+};
+
+// The side structs and every argument check, in the order callers see their errors.  With P == 0 it ends after the
+// checks an empty scene needs (as check_common does).
+static int bwd_check_args(BwdCall &c, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
+                          const gsr_features_ext *feat) {
+    const gsr_backward_args *a = c.a;
+    int rc = read_composite_ext(ext, a->background, c.e);
+    if (rc) return rc;
+    read_absgrad_ext(absgrad, c.ab);
+    rc = read_features_ext(feat, a->P, c.fx);
+    if (rc) return rc;
+    if (c.fx.given && c.ab.dL_dmeans2D_abs)
+        return fail(GSR_ERR_UNSUPPORTED, "features with gsr_absgrad_ext.dL_dmeans2D_abs are not built yet");
+    if (c.fx.given && a->stages != GSR_BWD_ALL)
+        return fail(GSR_ERR_UNSUPPORTED, "features with a split backward (stages != GSR_BWD_ALL) are not built yet");
+    c.feat_bwd = c.fx.given && c.fx.dL_dout_features != nullptr;
+    if (c.ab.densify_abs && !a->densify_stats)
+        return fail(GSR_ERR_ARG, "gsr_absgrad_ext.densify_abs needs densify_stats");
+    if (c.ab.densify_abs && !c.ab.dL_dmeans2D_abs)
+        return fail(GSR_ERR_ARG, "gsr_absgrad_ext.densify_abs needs dL_dmeans2D_abs");
+    if (a->stages == GSR_BWD_GAUSSIANS)  // the per-Gaussian stage reads no background: only its presence counts
+        c.e.out_alpha = nullptr, c.e.dL_dalpha = nullptr, c.e.dL_dbackground = c.e.dL_dbackground_image = nullptr;
+    rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
+                      a->scales, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
+                      c.e.background_image ? c.e.background_image : a->background);
+    if (rc) return rc;
+    if ((c.e.dL_dbackground || c.e.dL_dbackground_image) && !a->dL_dpix)
+        return fail(GSR_ERR_ARG, "dL_dpix is required for the background gradients");
+    if (a->P == 0) return GSR_OK;
+    if (!a->dL_dpix || !a->radii) return fail(GSR_ERR_ARG, "dL_dpix and radii are required");
+    if (!a->geom_buffer || !a->image_buffer || (a->R > 0 && !a->binning_buffer))
+        return fail(GSR_ERR_ARG, "forward buffers are required");
+    if (a->stages != GSR_BWD_COMPOSITE && a->shs && a->M > 0 && !a->dL_dsh && !a->dL_dcolors_sh)
+        return fail(GSR_ERR_ARG, "dL_dsh (or dL_dcolors_sh) is required when shs are given");
+    if (a->R < 0 || a->R > 0xffffffffLL) return fail(GSR_ERR_ARG, "bad num_rendered");
+    if (a->stages < GSR_BWD_ALL || a->stages > GSR_BWD_GAUSSIANS) return fail(GSR_ERR_ARG, "bad backward stages");
+    if (a->campos_rows && (!a->campos || a->campos_nrows < 1 || a->campos_rank < 0 || a->campos_rank >= a->campos_nrows))
+        return fail(GSR_ERR_ARG, "campos_rows needs campos and 0 <= campos_rank < campos_nrows");
+    c.g0 = a->g_begin, c.g1 = a->g_end;
+    if (c.g0 == 0 && c.g1 == 0) c.g1 = a->P;
+    if (c.g0 < 0 || c.g1 < c.g0 || c.g1 > a->P) return fail(GSR_ERR_ARG, "bad Gaussian range [g_begin, g_end)");
+    if (a->stages == GSR_BWD_GAUSSIANS && a->R > 0 && !a->bwd_scratch)
+        return fail(GSR_ERR_ARG, "GSR_BWD_GAUSSIANS needs the bwd_scratch of the GSR_BWD_COMPOSITE call");
+    if (a->num_big > a->P) return fail(GSR_ERR_ARG, "bad num_big");
+    return GSR_OK;
+}
+
+// The forward's buffers and this call's scratch (allocated here, or the composite call's for GSR_BWD_GAUSSIANS), carved
+static int bwd_carve(BwdCall &c) {
+    const gsr_backward_args *a = c.a;
+    c.gx = (a->W + BLOCK_X - 1) / BLOCK_X, c.gy = (a->H + BLOCK_Y - 1) / BLOCK_Y;
+    c.T = (uint32_t)(c.gx * c.gy);
+    c.R = (uint32_t)a->R;
+    carve_geom(a->geom_buffer, a->P, c.g);
+    carve_binning(a->binning_buffer, c.R, c.T, c.b);
+    carve_image(a->image_buffer, a->W, a->H, c.im);
+    c.nbig = a->num_big < 0 ? c.R / (BIG_GAUSSIAN_TILES + 1) + 1 : (uint32_t)a->num_big;
+    c.nbig_dev = a->num_big < 0 ? c.g.counters + CNT_BIG : nullptr;
+    const bool abs = c.ab.dL_dmeans2D_abs != nullptr;
+    const int fb = c.feat_bwd ? feat_block(c.fx.C) : 0;
+    char *scratch = a->bwd_scratch;
+    if (a->stages != GSR_BWD_GAUSSIANS) {
+        scratch = c.alloc(c.alloc_ctx, GSR_BUF_BWD_SCRATCH, bwd_scratch_size(c.R, c.nbig, abs, fb));
+        if (!scratch) return fail(GSR_ERR_ALLOC, "backward scratch allocation failed");
+    }
+    carve_bwd_scratch(scratch, c.R, c.nbig, abs, fb, c.sc);
+    c.src.radii = a->radii; c.src.tiles = c.g.tiles; c.src.inst_start = c.g.inst_start;
+    c.src.big_slot = c.g.big_slot; c.src.big_list = c.g.big_list; c.src.inv = c.b.inv;
+    c.src.live = tuning("bwd_live", 1) ? c.g.live : nullptr;
+    c.src.live_valid = c.g.counters + CNT_LIVE_VALID;
+    return GSR_OK;
+}
+
+// Compositing backward: the instance gradient rows (and abs rows), the live flags, the zero fill of the outputs
+static int bwd_composite(BwdCall &c) {
+    const gsr_backward_args *a = c.a;
+    hipStream_t stream = c.stream;
+    RenderBwdParams rp;
+    rp.W = a->W; rp.H = a->H; rp.gx = c.gx; rp.gy = c.gy; rp.num_tiles = (int)c.T; rp.num_rendered = c.R;
+    rp.ranges = c.im.ranges; rp.point_list = c.b.point_list; rp.n_contrib = c.im.n_contrib;
+    const int lpt = tuning("lpt", 1);
+    // the backward's own order (by tile_last; reusing the forward's range-length order measured slower)
+    const bool own_order = lpt != 0;
+    // in lpt_append_range the forward's whole-tile waves filled the bucket lists (render_bwd falls back to the
+    // identity order if that forward did not, *lpt_valid = 0: the order never changes a result)
+    const bool lists = own_order && lpt_append_range(c.T) && tuning("lpt_append", 1);
+    if (own_order && !lists)
+        launch_tile_order(stream, c.im.ranges, c.im.tile_last, 1, (int)c.T, c.im.order_bwd, c.im.lpt_hist);
+    rp.tile_order = lpt ? (own_order ? (lists ? nullptr : c.im.order_bwd) : c.im.order_fwd) : nullptr;
+    if (lists) {
+        rp.lpt_bcnt = c.im.lpt_bcnt; rp.lpt_blist = c.im.lpt_blist; rp.lpt_valid = c.im.lpt_valid;
+    }
+    rp.tile_last = c.im.tile_last; rp.tile_loaded = c.im.tile_loaded;
+    rp.rec = c.g.rec;
+    rp.bg = a->background ? a->background : c.e.background_image; rp.bg_image = c.e.background_image;
+    rp.dL_dalpha = c.e.dL_dalpha;
+    rp.final_T = c.im.final_T; rp.dL_dpix = a->dL_dpix; rp.dL_dinvdepth = a->dL_dinvdepth;
+    rp.rows = c.sc.rows;
+    rp.abs_rows = c.sc.abs_rows;
+    rp.live = c.src.live ? c.g.live : nullptr;
+    rp.live_valid = c.g.counters + CNT_LIVE_VALID;
+    rp.sorted_u = c.b.sorted_u;
+    rp.strip_mask = c.b.strip_mask; rp.smask_valid = c.im.smask_valid;
+    if (c.T <= SEG_MAX_TILES && tuning("bwd_seg", 1)) {  // segmented walk (from the forward's checkpoints, if any)
+        rp.ckpt = c.b.ckpt; rp.ctot = c.im.ctot; rp.ck_flag = c.im.ck_flag;
+        rp.seg_list = c.b.seg_list; rp.seg_count = c.im.seg_count;
+    }
+    const bool planned = a->stages == GSR_BWD_ALL && tuning("bwd_prezero", 1) &&
+                         zero_fill_plan(a, c.ab.dL_dmeans2D_abs, c.g0, c.g1, rp);
+    bool launched = false;
+    GSR_STAGE(ST_RENDER_BWD, c.dbg, launched = launch_render_bwd(stream, rp));
+    c.prezeroed = planned && launched;  // (the fill is the composite's: no launch, no zeros)
+    return GSR_OK;
+}
+
+// Channel block after channel block: the walk adds the block's geometry terms into the rows render_bwd just wrote (and
+// marks the live flags), then the block's feature rows are gathered into dL_dfeatures, so one block's rows are all the
+// scratch there is.  big_reduce then sums rows that hold every term.
+static int bwd_features(BwdCall &c) {
+    const gsr_backward_args *a = c.a;
+    hipStream_t stream = c.stream;
+    FeatBwdParams fp;
+    fp.W = a->W; fp.H = a->H; fp.gx = c.gx; fp.gy = c.gy; fp.num_tiles = (int)c.T; fp.C = c.fx.C;
+    fp.ranges = c.im.ranges; fp.point_list = c.b.point_list; fp.n_contrib = c.im.n_contrib;
+    fp.tile_last = c.im.tile_last; fp.tile_loaded = c.im.tile_loaded; fp.sorted_u = c.b.sorted_u;
+    fp.rec = c.g.rec; fp.final_T = c.im.final_T; fp.features = c.fx.features; fp.dL_dF = c.fx.dL_dout_features;
+    fp.rows = c.sc.rows; fp.frows = c.sc.feat_rows;
+    fp.live = c.src.live ? c.g.live : nullptr; fp.strip_exact = 1;
+    FeatGatherParams gp;
+    gp.P = a->P; gp.C = c.fx.C;
+    gp.src = c.src;
+    gp.frows = c.sc.feat_rows; gp.bigsum = c.sc.feat_bigsum;
+    gp.nbig = c.nbig; gp.nbig_dev = c.nbig_dev;
+    gp.out = c.fx.dL_dfeatures;
+    const int fb = feat_block(c.fx.C);
+    for (int c0 = 0; c0 < c.fx.C; c0 += fb) {
+        fp.c0 = gp.c0 = c0;
+        GSR_STAGE(ST_FEAT_BWD, c.dbg, launch_feat_bwd(stream, fp));
+        if (gp.out) GSR_STAGE(ST_FEAT_GATHER, c.dbg, launch_feat_gather(stream, gp));
+    }
+    return GSR_OK;
+}
+
+// The big Gaussians' rows (and abs rows), summed by a workgroup each
+static int bwd_big_reduce(BwdCall &c) {
+    hipStream_t stream = c.stream;
+    BigReduceParams bp;
+    bp.src = c.src;
+    bp.rows = c.sc.rows; bp.bigsum = c.sc.bigsum;
+    bp.abs_rows = c.sc.abs_rows; bp.bigsum_abs = c.sc.bigsum_abs;
+    bp.nbig_dev = c.nbig_dev;
+    GSR_STAGE(ST_BIG_REDUCE, c.dbg, launch_big_reduce(stream, bp, c.nbig));
+    return GSR_OK;
+}
+
+// Per-Gaussian stage over [g0, g1): the rows gathered, the preprocess backward, the camera sums, the abs gather
+static int bwd_gaussians(BwdCall &c) {
+    const gsr_backward_args *a = c.a;
+    hipStream_t stream = c.stream;
+    const int64_t g0 = c.g0, g1 = c.g1;
+    // Chunk-relative outputs (a split backward) address Gaussian g0's row: shift them so the kernel indexes every
+    // output by the absolute Gaussian index (integer arithmetic: the shifted address is never dereferenced)
+    auto rel = [g0](auto *ptr, int64_t width) -> decltype(ptr) {
+        if (!ptr || g0 == 0) return ptr;
+        return reinterpret_cast<decltype(ptr)>(reinterpret_cast<uintptr_t>(ptr) - (uintptr_t)(g0 * width) * sizeof(*ptr));
+    };
+    PreprocessBwdParams pp;
+    pp.P = a->P; pp.D = a->D; pp.M = a->M; pp.W = a->W; pp.H = a->H;
+    pp.g0 = (int)g0; pp.g1 = (int)g1;
+    pp.tan_fovx = a->tan_fovx; pp.tan_fovy = a->tan_fovy;
+    pp.focal_x = a->W / (2.0f * a->tan_fovx);
+    pp.focal_y = a->H / (2.0f * a->tan_fovy);
+    pp.scale_modifier = a->scale_modifier;
+    pp.antialiasing = a->antialiasing;
+    pp.has_invdepth = a->dL_dinvdepth != nullptr;
+    pp.means3D = a->means3D; pp.opacities = a->opacities; pp.scales = a->scales; pp.rotations = a->rotations;
+    pp.cov3D_precomp = a->cov3D_precomp; pp.shs = (a->colors_precomp ? nullptr : a->shs);
+    pp.view = a->viewmatrix; pp.proj = a->projmatrix; pp.campos = a->campos;
+    pp.src = c.src;
+    pp.clamped = c.g.clamped;
+    pp.sh_jac = c.g.sh_jac;  // the forward's d rgb / d dir: the SH term of dL/dmeans3D reads no coefficient
+    pp.bigsum = c.sc.bigsum;
+    pp.rows = c.sc.rows;
+    pp.sh_vec16 = pp.shs && a->M == 16 && (((uintptr_t)pp.shs | (uintptr_t)a->dL_dsh) & 15) == 0;
+    pp.dL_dmeans2D = rel(a->dL_dmeans2D, 3); pp.dL_dcolors = rel(a->dL_dcolors, 3);
+    pp.dL_dopacity = rel(a->dL_dopacity, 1); pp.dL_dmeans3D = rel(a->dL_dmeans3D, 3);
+    pp.dL_dcov3D = rel(a->dL_dcov3D, 6); pp.dL_dsh = rel(a->dL_dsh, (int64_t)a->M * 3);
+    pp.dL_dcolors_sh = rel(a->dL_dcolors_sh, 3);
+    pp.densify_stats = c.ab.densify_abs ? nullptr : rel(a->densify_stats, 2);  // (densify_abs: written by the abs gather)
+    pp.densify_accumulate = a->densify_accumulate;
+    pp.max_radii2D = rel(a->max_radii2D, 1);
+    pp.dL_dscales = rel(a->dL_dscales, 3); pp.dL_drot = rel(a->dL_drotations, 4);
+    pp.campos_rows = a->campos_rows; pp.campos_rank = a->campos_rank; pp.campos_nrows = a->campos_nrows;
+    pp.prezeroed = c.prezeroed ? 1 : 0;
+    const size_t ng = (size_t)(g1 - g0);
+    if (pp.shs == nullptr && a->dL_dsh && a->M > 0)
+        GSR_HIP(hipMemsetAsync(a->dL_dsh, 0, sizeof(float) * ng * a->M * 3, stream));
+    if (pp.shs == nullptr && a->dL_dcolors_sh)
+        GSR_HIP(hipMemsetAsync(a->dL_dcolors_sh, 0, sizeof(float) * ng * 3, stream));
+    if (camera_grads(a)) {
+        if (ng == 0) return zero_camera_grads(a, stream);
+        pp.cam_partials = reinterpret_cast<float *>(c.alloc(c.alloc_ctx, GSR_BUF_CAMERA_PARTIALS, camera_partials_bytes((int64_t)ng)));
+        if (!pp.cam_partials) return fail(GSR_ERR_ALLOC, "camera partials allocation failed");
+    }
+    AbsGatherParams gp{};
+    if (c.ab.dL_dmeans2D_abs) {
+        gp.g0 = (int)g0; gp.g1 = (int)g1;
+        gp.src = c.src;
+        gp.abs_rows = c.sc.abs_rows; gp.bigsum_abs = c.sc.bigsum_abs;
+        gp.out = rel(c.ab.dL_dmeans2D_abs, 2);
+        gp.densify_stats = c.ab.densify_abs ? rel(a->densify_stats, 2) : nullptr;
+        gp.densify_accumulate = a->densify_accumulate;
+        gp.prezeroed = pp.prezeroed;
+    }
+    GSR_STAGE(ST_PREPROCESS_BWD, c.dbg, {
+        launch_preprocess_bwd(stream, pp);
+        if (pp.cam_partials) launch_camera_reduce(stream, pp, a->dL_dviewmatrix, a->dL_dprojmatrix, a->dL_dcampos);
+        if (c.ab.dL_dmeans2D_abs) launch_abs_gather(stream, gp);
+    });
+    return GSR_OK;
+}
+
 int gsr_backward(const gsr_backward_args *a, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr) {
     return gsr_backward_ext(a, nullptr, alloc, alloc_ctx, stream_ptr);
 }
@@ -928,227 +1187,37 @@ int gsr_backward_abs(const gsr_backward_args *a, const gsr_composite_ext *ext, c
 int gsr_backward_features(const gsr_backward_args *a, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
                           const gsr_features_ext *feat, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr) {
     if (!a || !alloc) return fail(GSR_ERR_ARG, "null argument");
-    CompositeExt e;
-    int rc = read_composite_ext(ext, a->background, e);
+    BwdCall c{};
+    c.a = a; c.alloc = alloc; c.alloc_ctx = alloc_ctx;
+    c.stream = (hipStream_t)stream_ptr; c.dbg = a->debug != 0;
+    hipStream_t stream = c.stream;
+    int rc = bwd_check_args(c, ext, absgrad, feat);
     if (rc) return rc;
-    AbsgradExt ab;
-    read_absgrad_ext(absgrad, ab);
-    FeaturesExt fx;
-    rc = read_features_ext(feat, a->P, fx);
-    if (rc) return rc;
-    if (fx.given && ab.dL_dmeans2D_abs)
-        return fail(GSR_ERR_UNSUPPORTED, "features with gsr_absgrad_ext.dL_dmeans2D_abs are not built yet");
-    if (fx.given && a->stages != GSR_BWD_ALL)
-        return fail(GSR_ERR_UNSUPPORTED, "features with a split backward (stages != GSR_BWD_ALL) are not built yet");
-    // the feature work of this call: only with an upstream gradient of the feature image
-    const bool feat_bwd = fx.given && fx.dL_dout_features != nullptr;
-    if (ab.densify_abs && !a->densify_stats)
-        return fail(GSR_ERR_ARG, "gsr_absgrad_ext.densify_abs needs densify_stats");
-    if (ab.densify_abs && !ab.dL_dmeans2D_abs)
-        return fail(GSR_ERR_ARG, "gsr_absgrad_ext.densify_abs needs dL_dmeans2D_abs");
-    if (a->stages == GSR_BWD_GAUSSIANS)  // the per-Gaussian stage reads no background: only its presence counts
-        e.out_alpha = nullptr, e.dL_dalpha = nullptr, e.dL_dbackground = e.dL_dbackground_image = nullptr;
-    rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
-                      a->scales, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
-                      e.background_image ? e.background_image : a->background);
-    if (rc) return rc;
-    const bool bg_grads = e.dL_dbackground || e.dL_dbackground_image;
-    if (bg_grads && !a->dL_dpix) return fail(GSR_ERR_ARG, "dL_dpix is required for the background gradients");
-    if (a->P == 0) {
-        if (!camera_grads(a) && !bg_grads) return GSR_OK;
-        StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
-        rc = background_grads(a, e, nullptr, alloc, alloc_ctx, (hipStream_t)stream_ptr);  // T_final = 1
+    if (a->P == 0) {  // no Gaussian: the background's gradients with T_final = 1, the camera's empty sums
+        if (!camera_grads(a) && !c.e.dL_dbackground && !c.e.dL_dbackground_image) return GSR_OK;
+        StreamDeviceGuard device_guard(stream);
+        rc = background_grads(a, c.e, nullptr, alloc, alloc_ctx, stream);
         if (rc) return rc;
-        return camera_grads(a) ? zero_camera_grads(a, (hipStream_t)stream_ptr) : GSR_OK;
+        return camera_grads(a) ? zero_camera_grads(a, stream) : GSR_OK;
     }
-    if (!a->dL_dpix || !a->radii) return fail(GSR_ERR_ARG, "dL_dpix and radii are required");
-    if (!a->geom_buffer || !a->image_buffer || (a->R > 0 && !a->binning_buffer))
-        return fail(GSR_ERR_ARG, "forward buffers are required");
-    if (a->stages != GSR_BWD_COMPOSITE && a->shs && a->M > 0 && !a->dL_dsh && !a->dL_dcolors_sh)
-        return fail(GSR_ERR_ARG, "dL_dsh (or dL_dcolors_sh) is required when shs are given");
-    if (a->R < 0 || a->R > 0xffffffffLL) return fail(GSR_ERR_ARG, "bad num_rendered");
-    if (a->stages < GSR_BWD_ALL || a->stages > GSR_BWD_GAUSSIANS) return fail(GSR_ERR_ARG, "bad backward stages");
-    if (a->campos_rows && (!a->campos || a->campos_nrows < 1 || a->campos_rank < 0 || a->campos_rank >= a->campos_nrows))
-        return fail(GSR_ERR_ARG, "campos_rows needs campos and 0 <= campos_rank < campos_nrows");
-    int64_t g0 = a->g_begin, g1 = a->g_end;
-    if (g0 == 0 && g1 == 0) g1 = a->P;
-    if (g0 < 0 || g1 < g0 || g1 > a->P) return fail(GSR_ERR_ARG, "bad Gaussian range [g_begin, g_end)");
-    if (a->stages == GSR_BWD_GAUSSIANS && a->R > 0 && !a->bwd_scratch)
-        return fail(GSR_ERR_ARG, "GSR_BWD_GAUSSIANS needs the bwd_scratch of the GSR_BWD_COMPOSITE call");
-    hipStream_t stream = (hipStream_t)stream_ptr;
     StreamDeviceGuard device_guard(stream);
-    const bool dbg = a->debug != 0;
-    const int P = a->P, W = a->W, H = a->H;
-    const int gx = (W + BLOCK_X - 1) / BLOCK_X, gy = (H + BLOCK_Y - 1) / BLOCK_Y;
-    const uint32_t T = (uint32_t)(gx * gy);
-    const uint32_t R = (uint32_t)a->R;
-
-    GeomState g;
-    carve_geom(a->geom_buffer, P, g);
-    BinningState b;
-    carve_binning(a->binning_buffer, R, T, b);
-    ImageState im;
-    carve_image(a->image_buffer, W, H, im);
-    if (a->num_big > a->P) return fail(GSR_ERR_ARG, "bad num_big");
-    // num_big < 0: not known on the host (the upstream backward signature has no such argument, gsr_torch_ext):
-    // size the big-Gaussian sums for the most there can be (each has > BIG_GAUSSIAN_TILES instances) and let the
-    // reduction read the count the preprocess left in the geometry buffer
-    const bool nbig_on_device = a->num_big < 0;
-    const uint32_t nbig = nbig_on_device ? R / (BIG_GAUSSIAN_TILES + 1) + 1 : (uint32_t)a->num_big;
-    char *scratch = a->stages == GSR_BWD_GAUSSIANS ? a->bwd_scratch
-                                                   : alloc(alloc_ctx, GSR_BUF_BWD_SCRATCH,
-                                                           feat_bwd ? bwd_scratch_bytes_features(R, nbig, feat_block(fx.C))
-                                                           : ab.dL_dmeans2D_abs ? bwd_scratch_bytes_abs(R, nbig)
-                                                                                : bwd_scratch_bytes(R, nbig));
-    if (!scratch && a->stages != GSR_BWD_GAUSSIANS) return fail(GSR_ERR_ALLOC, "backward scratch allocation failed");
-    float *rows = reinterpret_cast<float *>(scratch);
-    // Gaussian-major gradient rows: render_bwd scatters its 40-B rows to the instances' expansion indices so
-    // the per-Gaussian gather in preprocess_bwd reads each Gaussian's rows contiguously.
-    float *bigsum = bwd_bigsum_ptr(scratch, R);
-    // the 8-B abs rows and their big-Gaussian sums, behind them (only with gsr_absgrad_ext.dL_dmeans2D_abs)
-    float2 *abs_rows = nullptr, *bigsum_abs = nullptr;
-    if (ab.dL_dmeans2D_abs && scratch) {
-        abs_rows = reinterpret_cast<float2 *>(bwd_abs_rows_ptr(scratch, R, nbig));
-        bigsum_abs = reinterpret_cast<float2 *>(bwd_abs_bigsum_ptr(scratch, R, nbig));
-    }
-
-    bool prezero = false;  // the composite zero-fills the per-Gaussian outputs (zero_fill_plan)
-    if (R > 0 && a->stages != GSR_BWD_GAUSSIANS) {
-        RenderBwdParams rp;
-        rp.W = W; rp.H = H; rp.gx = gx; rp.gy = gy; rp.num_tiles = (int)T; rp.num_rendered = R;
-        rp.ranges = im.ranges; rp.point_list = b.point_list; rp.n_contrib = im.n_contrib;
-        const int lpt = tuning("lpt", 1);
-        // the backward's own order (by tile_last; reusing the forward's range-length order measured slower)
-        const bool own_order = lpt != 0;
-        // in lpt_append_range the forward's whole-tile waves filled the bucket lists (render_bwd falls back to the
-        // identity order if that forward did not, *lpt_valid = 0: the order never changes a result)
-        const bool lists = own_order && lpt_append_range(T) && tuning("lpt_append", 1);
-        if (own_order && !lists)
-            launch_tile_order(stream, im.ranges, im.tile_last, 1, (int)T, im.order_bwd, im.lpt_hist);
-        rp.tile_order = lpt ? (own_order ? (lists ? nullptr : im.order_bwd) : im.order_fwd) : nullptr;
-        if (lists) {
-            rp.lpt_bcnt = im.lpt_bcnt; rp.lpt_blist = im.lpt_blist; rp.lpt_valid = im.lpt_valid;
+    rc = bwd_carve(c);
+    if (rc) return rc;
+    if (a->stages != GSR_BWD_GAUSSIANS) {
+        if (c.R > 0) {
+            rc = bwd_composite(c);
+            if (!rc && c.feat_bwd) rc = bwd_features(c);
+            if (!rc) rc = bwd_big_reduce(c);
+            if (rc) return rc;
         }
-        rp.tile_last = im.tile_last; rp.tile_loaded = im.tile_loaded;
-        rp.rec = g.rec;
-        rp.bg = a->background ? a->background : e.background_image; rp.bg_image = e.background_image; rp.dL_dalpha = e.dL_dalpha;
-        rp.final_T = im.final_T; rp.dL_dpix = a->dL_dpix; rp.dL_dinvdepth = a->dL_dinvdepth;
-        rp.rows = rows;
-        rp.abs_rows = abs_rows;
-        rp.live = tuning("bwd_live", 1) ? g.live : nullptr;
-        rp.live_valid = g.counters + CNT_LIVE_VALID;
-        rp.sorted_u = b.sorted_u;
-        rp.strip_mask = b.strip_mask; rp.smask_valid = im.smask_valid;
-        if (T <= SEG_MAX_TILES && tuning("bwd_seg", 1)) {  // segmented walk (from the forward's checkpoints, if any)
-            rp.ckpt = b.ckpt; rp.ctot = im.ctot; rp.ck_flag = im.ck_flag;
-            rp.seg_list = b.seg_list; rp.seg_count = im.seg_count;
-        }
-        if (a->stages == GSR_BWD_ALL && tuning("bwd_prezero", 1)) prezero = zero_fill_plan(a, ab.dL_dmeans2D_abs, g0, g1, rp);
-        GSR_STAGE(ST_RENDER_BWD, dbg, launch_render_bwd(stream, rp));
-        if (feat_bwd) {
-            // Channel block after channel block: the walk adds the block's geometry terms into the rows render_bwd just
-            // wrote (and marks the live flags), then the block's feature rows are gathered into dL_dfeatures, so one
-            // block's rows are all the scratch there is.  big_reduce below then sums rows that hold every term.
-            const int fb = feat_block(fx.C);
-            FeatBwdParams fp;
-            fp.W = W; fp.H = H; fp.gx = gx; fp.gy = gy; fp.num_tiles = (int)T; fp.C = fx.C;
-            fp.ranges = im.ranges; fp.point_list = b.point_list; fp.n_contrib = im.n_contrib;
-            fp.tile_last = im.tile_last; fp.tile_loaded = im.tile_loaded; fp.sorted_u = b.sorted_u;
-            fp.rec = g.rec; fp.final_T = im.final_T; fp.features = fx.features; fp.dL_dF = fx.dL_dout_features;
-            fp.rows = rows; fp.frows = reinterpret_cast<float *>(bwd_feat_rows_ptr(scratch, R, nbig));
-            fp.live = rp.live; fp.strip_exact = 1;
-            FeatGatherParams gp;
-            gp.P = P; gp.C = fx.C;
-            gp.radii = a->radii; gp.tiles = g.tiles; gp.inst_start = g.inst_start; gp.big_slot = g.big_slot;
-            gp.big_list = g.big_list; gp.inv = b.inv;
-            gp.live = rp.live; gp.live_valid = rp.live_valid;
-            gp.frows = fp.frows; gp.bigsum = reinterpret_cast<float *>(bwd_feat_bigsum_ptr(scratch, R, nbig, fb));
-            gp.nbig = nbig; gp.nbig_dev = nbig_on_device ? g.counters + CNT_BIG : nullptr;
-            gp.out = fx.dL_dfeatures;
-            for (int c0 = 0; c0 < fx.C; c0 += fb) {
-                fp.c0 = gp.c0 = c0;
-                GSR_STAGE(ST_FEAT_BWD, dbg, launch_feat_bwd(stream, fp));
-                if (gp.out) GSR_STAGE(ST_FEAT_GATHER, dbg, launch_feat_gather(stream, gp));
-            }
-        }
-        BigReduceParams bp;
-        bp.big_list = g.big_list; bp.inst_start = g.inst_start; bp.tiles = g.tiles;
-        bp.inv = b.inv;
-        bp.rows = rows; bp.bigsum = bigsum;
-        bp.abs_rows = abs_rows; bp.bigsum_abs = bigsum_abs;
-        bp.nbig_dev = nbig_on_device ? g.counters + CNT_BIG : nullptr;
-        GSR_STAGE(ST_BIG_REDUCE, dbg, launch_big_reduce(stream, bp, nbig));
-    }
-    if (a->stages != GSR_BWD_GAUSSIANS) {  // (with nothing rendered the forward left final_T = 1 everywhere)
-        rc = background_grads(a, e, im.final_T, alloc, alloc_ctx, stream);
+        // (with nothing rendered the forward left final_T = 1 everywhere)
+        rc = background_grads(a, c.e, c.im.final_T, alloc, alloc_ctx, stream);
         if (rc) return rc;
     }
-    if (fx.dL_dfeatures && !(feat_bwd && R > 0))  // no upstream gradient, or nothing rendered: the empty sums
-        GSR_HIP(hipMemsetAsync(fx.dL_dfeatures, 0, sizeof(float) * (size_t)P * fx.C, stream));
+    if (c.fx.dL_dfeatures && !(c.feat_bwd && c.R > 0))  // no upstream gradient, or nothing rendered: the empty sums
+        GSR_HIP(hipMemsetAsync(c.fx.dL_dfeatures, 0, sizeof(float) * (size_t)a->P * c.fx.C, stream));
     if (a->stages == GSR_BWD_COMPOSITE) return GSR_OK;
-    // Chunk-relative outputs (a split backward) address Gaussian g0's row: shift them so the kernel indexes every
-    // output by the absolute Gaussian index (integer arithmetic: the shifted address is never dereferenced)
-    auto rel = [g0](auto *ptr, int64_t width) -> decltype(ptr) {
-        if (!ptr || g0 == 0) return ptr;
-        return reinterpret_cast<decltype(ptr)>(reinterpret_cast<uintptr_t>(ptr) - (uintptr_t)(g0 * width) * sizeof(*ptr));
-    };
-    PreprocessBwdParams pp;
-    pp.P = P; pp.D = a->D; pp.M = a->M; pp.W = W; pp.H = H;
-    pp.g0 = (int)g0; pp.g1 = (int)g1;
-    pp.tan_fovx = a->tan_fovx; pp.tan_fovy = a->tan_fovy;
-    pp.focal_x = W / (2.0f * a->tan_fovx);
-    pp.focal_y = H / (2.0f * a->tan_fovy);
-    pp.scale_modifier = a->scale_modifier;
-    pp.antialiasing = a->antialiasing;
-    pp.has_invdepth = a->dL_dinvdepth != nullptr;
-    pp.means3D = a->means3D; pp.opacities = a->opacities; pp.scales = a->scales; pp.rotations = a->rotations;
-    pp.cov3D_precomp = a->cov3D_precomp; pp.shs = (a->colors_precomp ? nullptr : a->shs);
-    pp.view = a->viewmatrix; pp.proj = a->projmatrix; pp.campos = a->campos;
-    pp.radii = a->radii; pp.tiles = g.tiles; pp.inst_start = g.inst_start; pp.clamped = g.clamped;
-    pp.live = tuning("bwd_live", 1) ? g.live : nullptr;
-    pp.live_valid = g.counters + CNT_LIVE_VALID;
-    pp.inv = b.inv;
-    pp.sh_jac = g.sh_jac;  // the forward's d rgb / d dir: the SH term of dL/dmeans3D reads no coefficient
-    pp.big_slot = g.big_slot; pp.bigsum = bigsum;
-    pp.rows = rows;
-    pp.sh_vec16 = pp.shs && a->M == 16 && (((uintptr_t)pp.shs | (uintptr_t)a->dL_dsh) & 15) == 0;
-    pp.dL_dmeans2D = rel(a->dL_dmeans2D, 3); pp.dL_dcolors = rel(a->dL_dcolors, 3);
-    pp.dL_dopacity = rel(a->dL_dopacity, 1); pp.dL_dmeans3D = rel(a->dL_dmeans3D, 3);
-    pp.dL_dcov3D = rel(a->dL_dcov3D, 6); pp.dL_dsh = rel(a->dL_dsh, (int64_t)a->M * 3);
-    pp.dL_dcolors_sh = rel(a->dL_dcolors_sh, 3);
-    pp.densify_stats = ab.densify_abs ? nullptr : rel(a->densify_stats, 2);  // (densify_abs: written by the abs gather)
-    pp.densify_accumulate = a->densify_accumulate;
-    pp.max_radii2D = rel(a->max_radii2D, 1);
-    pp.dL_dscales = rel(a->dL_dscales, 3); pp.dL_drot = rel(a->dL_drotations, 4);
-    pp.campos_rows = a->campos_rows; pp.campos_rank = a->campos_rank; pp.campos_nrows = a->campos_nrows;
-    pp.prezeroed = prezero ? 1 : 0;
-    const size_t ng = (size_t)(g1 - g0);
-    if (pp.shs == nullptr && a->dL_dsh && a->M > 0)
-        GSR_HIP(hipMemsetAsync(a->dL_dsh, 0, sizeof(float) * ng * a->M * 3, stream));
-    if (pp.shs == nullptr && a->dL_dcolors_sh)
-        GSR_HIP(hipMemsetAsync(a->dL_dcolors_sh, 0, sizeof(float) * ng * 3, stream));
-    if (camera_grads(a)) {
-        if (ng == 0) return zero_camera_grads(a, stream);
-        pp.cam_partials = reinterpret_cast<float *>(alloc(alloc_ctx, GSR_BUF_CAMERA_PARTIALS, camera_partials_bytes((int64_t)ng)));
-        if (!pp.cam_partials) return fail(GSR_ERR_ALLOC, "camera partials allocation failed");
-    }
-    AbsGatherParams gp{};
-    if (ab.dL_dmeans2D_abs) {
-        gp.g0 = (int)g0; gp.g1 = (int)g1;
-        gp.radii = a->radii; gp.tiles = g.tiles; gp.inst_start = g.inst_start; gp.big_slot = g.big_slot; gp.inv = b.inv;
-        gp.live = pp.live; gp.live_valid = pp.live_valid;
-        gp.abs_rows = abs_rows; gp.bigsum_abs = bigsum_abs;
-        gp.out = rel(ab.dL_dmeans2D_abs, 2);
-        gp.densify_stats = ab.densify_abs ? rel(a->densify_stats, 2) : nullptr;
-        gp.densify_accumulate = a->densify_accumulate;
-        gp.prezeroed = prezero ? 1 : 0;
-    }
-    GSR_STAGE(ST_PREPROCESS_BWD, dbg, {
-        launch_preprocess_bwd(stream, pp);
-        if (pp.cam_partials) launch_camera_reduce(stream, pp, a->dL_dviewmatrix, a->dL_dprojmatrix, a->dL_dcampos);
-        if (ab.dL_dmeans2D_abs) launch_abs_gather(stream, gp);
-    });
-    return GSR_OK;
+    return bwd_gaussians(c);
 }
 
 int gsr_sh_backward_views_chunked(int P, int D, int M, int V, int64_t chunk_len, const float *means3D,

@@ -747,8 +747,8 @@ static void launch_parts(dim3 grid, dim3 block, hipStream_t s, const RenderBwdPa
     else render_bwd_parts_kernel<HAS_INV, PARTS><<<grid, block, 0, s>>>(q);
 }
 
-void launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
-    if (p.num_tiles <= 0) return;
+bool launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
+    if (p.num_tiles <= 0) return false;
     RenderBwdParams q = p;
     q.strip_exact = tuning("strip_exact", 1);
     q.stamps = tuning("stamp", 0) ? stamp_buffer(1) : nullptr;
@@ -762,7 +762,7 @@ void launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
         else if (gd) launch_v5<false, false, true, true>(grid, block, s, q);
         else if (p.dL_dinvdepth) launch_v5<true, false, true>(grid, block, s, q);
         else launch_v5<false, false, true>(grid, block, s, q);
-        return;
+        return true;
     }
     // "bwd_parts" 1, 2 or 4; 0 (default): 4 or 2 while that many part-waves fit within bwd_part_slots
     // (1024 SIMDs x 12: 800x800 (2500 tiles) takes 4 parts, 0.143 ms against 0.149 in 2 and 0.181 whole; 1080p
@@ -780,7 +780,7 @@ void launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
             if (parts == 2) launch_parts<false, 2>(grid, block, s, q);
             else launch_parts<false, 4>(grid, block, s, q);
         }
-        return;
+        return true;
     }
     // with the forward's bucket lists the slots run to xcd_slots(T) (per-XCD lists); the extra ones exit
     const dim3 grid(p.lpt_blist ? xcd_slots((uint32_t)p.num_tiles) : (uint32_t)p.num_tiles), block(64);
@@ -794,7 +794,7 @@ void launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
         else if (p.dL_dinvdepth) launch_v5<true, false, false, true>(grid, block, s, q);
         else if (u) launch_v5<false, true, false, true>(grid, block, s, q);
         else launch_v5<false, false, false, true>(grid, block, s, q);
-        return;
+        return true;
     }
     if (p.dL_dinvdepth) {
         if (u) launch_v5<true, true>(grid, block, s, q);
@@ -803,6 +803,7 @@ void launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
         if (u) launch_v5<false, true>(grid, block, s, q);
         else launch_v5<false>(grid, block, s, q);
     }
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -820,8 +821,8 @@ __global__ __launch_bounds__(256) void big_reduce_kernel(BigReduceParams p) {
     // the loop's live state took the kernel from 64 to 80 VGPRs, 8 to 6 waves, cfg 5 0.078 -> 0.12 ms)
     const uint32_t nb = PERSIST ? *p.nbig_dev : gridDim.x;
     for (uint32_t bi = blockIdx.x; bi < nb; bi += gridDim.x) {  // workgroup-uniform
-        const uint32_t gidx = p.big_list[bi];
-        const uint32_t start = p.inst_start[gidx], cnt = p.tiles[gidx];
+        const uint32_t gidx = p.src.big_list[bi];
+        const uint32_t start = p.src.inst_start[gidx], cnt = p.src.tiles[gidx];
         float acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         [[maybe_unused]] float acc_ax = 0.f, acc_ay = 0.f;
         // rows by expansion index (every cell of a big Gaussian's rect is an instance): BR_UNROLL inv words per thread
@@ -838,7 +839,7 @@ __global__ __launch_bounds__(256) void big_reduce_kernel(BigReduceParams p) {
 #pragma unroll
             for (int q = 0; q < BR_UNROLL; q++) {
                 const uint32_t k = k0 + 256 * q;
-                use[q] = k < cnt && p.inv[start + k] != INV_NONE;
+                use[q] = k < cnt && p.src.inv[start + k] != INV_NONE;
             }
             // (rows stay under `if (use)`: loading row 0 for the unwritten ones instead measured slower at cfg 5)
 #pragma unroll

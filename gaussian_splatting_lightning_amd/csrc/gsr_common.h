@@ -345,32 +345,33 @@ inline size_t carve_image(char *base, int W, int H, ImageState &im) {
     return c.off + 256;
 }
 
-// backward scratch: one gradient row per instance, then one summed row per big Gaussian
-inline size_t bwd_scratch_bytes(int64_t R, int64_t nbig) {
-    return align_up((size_t)(R ? R : 1) * GRAD_ROW * sizeof(float), 256) +
-           align_up((size_t)(nbig ? nbig : 1) * GRAD_ROW * sizeof(float), 256) + 256;
-}
-// with the absolute screen-space sums: behind that layout (unchanged), one 8-B row per instance, then one per big Gaussian
-inline size_t bwd_scratch_bytes_abs(int64_t R, int64_t nbig) {
-    return bwd_scratch_bytes(R, nbig) + align_up((size_t)(R ? R : 1) * 2 * sizeof(float), 256) +
-           align_up((size_t)(nbig ? nbig : 1) * 2 * sizeof(float), 256);
-}
-inline char *bwd_abs_rows_ptr(char *scratch, int64_t R, int64_t nbig) { return scratch + bwd_scratch_bytes(R, nbig); }
-inline char *bwd_abs_bigsum_ptr(char *scratch, int64_t R, int64_t nbig) {
-    return bwd_abs_rows_ptr(scratch, R, nbig) + align_up((size_t)(R ? R : 1) * 2 * sizeof(float), 256);
-}
-// with feature channels: behind the plain layout (unchanged), ONE channel block's feature rows (fb = 8 or 16 floats
-// per instance; the blocks are processed one after the other and reuse them), then one such row per big Gaussian
-inline size_t bwd_scratch_bytes_features(int64_t R, int64_t nbig, int fb) {
-    return bwd_scratch_bytes(R, nbig) + align_up((size_t)(R ? R : 1) * fb * sizeof(float), 256) +
-           align_up((size_t)(nbig ? nbig : 1) * fb * sizeof(float), 256);
-}
-inline char *bwd_feat_rows_ptr(char *scratch, int64_t R, int64_t nbig) { return scratch + bwd_scratch_bytes(R, nbig); }
-inline char *bwd_feat_bigsum_ptr(char *scratch, int64_t R, int64_t nbig, int fb) {
-    return bwd_feat_rows_ptr(scratch, R, nbig) + align_up((size_t)(R ? R : 1) * fb * sizeof(float), 256);
-}
-inline float *bwd_bigsum_ptr(char *scratch, int64_t R) {
-    return reinterpret_cast<float *>(scratch + align_up((size_t)(R ? R : 1) * GRAD_ROW * sizeof(float), 256));
+// Backward scratch.  The plain layout: one gradient row per instance (Gaussian-major: render_bwd scatters its 40-B rows
+// to the instances' expansion indices, so the per-Gaussian gather reads each Gaussian's rows contiguously), then one
+// summed row per big Gaussian.  Behind it, leaving it unchanged: with abs, the absolute screen-space sums' 8-B rows,
+// one per instance and then one per big Gaussian; with feat_block (8 or 16, 0: none), ONE channel block's feature rows
+// (feat_block floats per instance: the blocks are processed one after the other and reuse them) and one such row per
+// big Gaussian.  A null base returns the size only (and null pointers).
+struct BwdScratch {
+    float *rows, *bigsum;
+    float2 *abs_rows, *bigsum_abs;
+    float *feat_rows, *feat_bigsum;
+};
+inline size_t carve_bwd_scratch(char *base, int64_t R, int64_t nbig, bool abs, int feat_block, BwdScratch &s) {
+    Carver c(base);
+    const size_t nr = (size_t)(R ? R : 1), nb = (size_t)(nbig ? nbig : 1);
+    s = BwdScratch{};
+    s.rows = c.take<float>(nr * GRAD_ROW);
+    s.bigsum = c.take<float>(nb * GRAD_ROW);
+    c.off = align_up(c.off, 256) + 256;
+    if (abs) {
+        s.abs_rows = c.take<float2>(nr);
+        s.bigsum_abs = c.take<float2>(nb);
+    }
+    if (feat_block) {
+        s.feat_rows = c.take<float>(nr * feat_block);
+        s.feat_bigsum = c.take<float>(nb * feat_block);
+    }
+    return align_up(c.off, 256);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@
 // Gaussian's channels onto the pixel's upstream gradient enters dL/dalpha, the scalar "behind" accumulator follows
 // D <- D + alpha (g - D) from 0 (no background term), and both are linear in dL/dF, so a block's six moment sums are
 // formed with its own D and added.  One wave owns a tile's rows: a plain read-add-store, no atomics.
-#include "gsr_kernels.h"
+#include "gsr_gather.h"
 
 namespace gsr {
 
@@ -391,11 +391,11 @@ __global__ __launch_bounds__(256) void feat_big_reduce_kernel(FeatGatherParams p
     const int c = threadIdx.x % FB, kl = threadIdx.x / FB;
     const uint32_t nb = p.nbig_dev ? *p.nbig_dev : p.nbig;
     for (uint32_t bi = blockIdx.x; bi < nb; bi += gridDim.x) {  // workgroup-uniform
-        const uint32_t gidx = p.big_list[bi];
-        const uint32_t start = p.inst_start[gidx], cnt = p.tiles[gidx];
+        const uint32_t gidx = p.src.big_list[bi];
+        const uint32_t start = p.src.inst_start[gidx], cnt = p.src.tiles[gidx];
         float acc = 0.f;
         for (uint32_t k = (uint32_t)kl; k < cnt; k += KL)
-            if (p.inv[start + k] != INV_NONE) acc += p.frows[(size_t)(start + k) * FB + c];
+            if (p.src.inv[start + k] != INV_NONE) acc += p.frows[(size_t)(start + k) * FB + c];
         s_p[kl][c] = acc;
         __syncthreads();
         if (threadIdx.x < FB) {
@@ -408,8 +408,8 @@ __global__ __launch_bounds__(256) void feat_big_reduce_kernel(FeatGatherParams p
 }
 
 // Feature gather: dL_dfeatures[g][c0 .. c0 + FB) = the Gaussian's feature rows summed in instance order, under the
-// tests of launch_abs_gather (a positive radius, the live flag when the composite marked them, inv != INV_NONE per
-// instance); a big Gaussian takes feat_big_reduce_kernel's sum.  One thread per (Gaussian, channel): a Gaussian's FB
+// tests of every gather (gsr_gather.h: a positive radius, the live flag when the composite marked them, inv !=
+// INV_NONE per instance); a big Gaussian takes feat_big_reduce_kernel's sum.  One thread per (Gaussian, channel): a Gaussian's FB
 // threads read one 32- or 64-B row segment together.  Every element is written (exact zeros for a Gaussian that is
 // culled or that no pixel takes); 4-B stores, the output need only be 4-B aligned.
 template <int FB>
@@ -418,22 +418,18 @@ __global__ __launch_bounds__(256) void feat_gather_kernel(FeatGatherParams p) {
     const int64_t g = (int64_t)blockIdx.x * (256 / FB) + threadIdx.x / FB;
     if (g >= p.P || p.c0 + c >= p.C) return;
     float acc = 0.f;
-    if (p.radii[g] > 0 && (!p.live || !*p.live_valid || p.live[g])) {
-        const uint32_t start = p.inst_start[g], cnt = p.tiles[g];
+    if (gather_wanted(p.src, g, p.src.radii[g])) {
+        const uint32_t start = p.src.inst_start[g], cnt = p.src.tiles[g];
         if (cnt > BIG_GAUSSIAN_TILES) {
-            acc = p.bigsum[(size_t)p.big_slot[g] * FB + c];
+            acc = p.bigsum[(size_t)p.src.big_slot[g] * FB + c];
         } else {
             // four inv words, then four rows, in flight together (abs_gather_kernel's form); added in instance order
             for (uint32_t k0 = 0; k0 < cnt; k0 += 4) {
-                uint32_t iv[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) iv[j] = p.inv[start + min(k0 + j, cnt - 1)];  // unconditional (clamped)
+                bool use[4];
+                inv_use4(p.src, start, k0, cnt, use);
                 float rw[4];
 #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const bool use = k0 + j < cnt && iv[j] != INV_NONE;
-                    rw[j] = use ? p.frows[(size_t)(start + k0 + j) * FB + c] : 0.f;
-                }
+                for (int j = 0; j < 4; j++) rw[j] = use[j] ? p.frows[(size_t)(start + k0 + j) * FB + c] : 0.f;
 #pragma unroll
                 for (int j = 0; j < 4; j++) acc += rw[j];
             }

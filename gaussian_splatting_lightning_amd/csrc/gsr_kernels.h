@@ -220,7 +220,7 @@ struct RenderBwdParams {
     // expansion index like `rows`, or null: the kernels without them
     float2 *abs_rows = nullptr;
 };
-void launch_render_bwd(hipStream_t s, const RenderBwdParams &p);
+bool launch_render_bwd(hipStream_t s, const RenderBwdParams &p);  // false: nothing to launch (no tile)
 
 // ---- background gradients, empty-scene fill (gsr_background.hip) ----
 // dL/dbackground_image = final_T * dL_dpix (3,H,W) and / or dL/dbackground (3) = its sum over the pixels, in one pass
@@ -233,9 +233,19 @@ void launch_background_grad(hipStream_t s, size_t HW, const float *final_T, cons
 void launch_background_fill(hipStream_t s, size_t HW, const float *bg, const float *bg_image, float *out_color,
                             float *out_alpha);
 
-struct BigReduceParams {
-    const uint32_t *big_list, *inst_start, *tiles;
+// What every per-Gaussian gather of the backward's instance rows reads to decide which rows to add: filled once per
+// backward (gsr_api.hip) and embedded in the param structs of the kernels that gather (the decisions themselves:
+// gsr_gather.h)
+struct GatherSrc {
+    const int *radii;
+    const uint32_t *tiles, *inst_start, *big_slot, *big_list;
     const uint32_t *inv;  // the forward's inverse permutation: INV_NONE where the composite loaded no instance (no row)
+    const uint8_t *live;  // P: 0 = no non-zero row (the gather is skipped: zero sums), or null = gather every Gaussian
+    const uint32_t *live_valid;  // the flags are used only when the last composite marked them
+};
+
+struct BigReduceParams {
+    GatherSrc src;
     const float *rows;
     float *bigsum;  // nbig x GRAD_ROW
     const uint32_t *nbig_dev;  // or null: the launch's nbig is exact; else an upper bound and this the count
@@ -254,12 +264,8 @@ struct PreprocessBwdParams {
     int sh_vec16;  // M == 16 and shs / dL_dsh 16-byte aligned: vectorised SH path
     const float *means3D, *opacities, *scales, *rotations, *cov3D_precomp, *shs;
     const float *view, *proj, *campos;
-    const int *radii;
-    const uint32_t *tiles, *inst_start, *big_slot;
-    const uint32_t *inv;  // the forward's inverse permutation: INV_NONE where the composite loaded no instance (no row)
+    GatherSrc src;
     const uint8_t *clamped;
-    const uint8_t *live;  // P: 0 = no non-zero row (the gather is skipped: zero sums), or null = gather every Gaussian
-    const uint32_t *live_valid;  // the flags are used only when the last composite marked them
     const float *sh_jac;  // 9 x P direction Jacobian of the colour, from the forward (SH degree > 0)
     const float *rows, *bigsum;
     float *dL_dmeans2D, *dL_dcolors, *dL_dopacity, *dL_dmeans3D, *dL_dcov3D, *dL_dsh, *dL_dscales, *dL_drot;
@@ -279,10 +285,7 @@ void launch_preprocess_bwd(hipStream_t s, const PreprocessBwdParams &p);
 // per-Gaussian kernel is then not given) is written here, [i][0] from the absolute sums.
 struct AbsGatherParams {
     int g0, g1;
-    const int *radii;
-    const uint32_t *tiles, *inst_start, *big_slot, *inv;
-    const uint8_t *live;
-    const uint32_t *live_valid;
+    GatherSrc src;
     const float2 *abs_rows, *bigsum_abs;
     float *out;            // (P,2), indexed by the absolute Gaussian index
     float *densify_stats;  // (P,2) or null (abs_stats)
@@ -328,10 +331,7 @@ void launch_feat_bwd(hipStream_t s, const FeatBwdParams &p);
 // feat_block(C) floats), which the launch fills first
 struct FeatGatherParams {
     int P, C, c0;
-    const int *radii;
-    const uint32_t *tiles, *inst_start, *big_slot, *big_list, *inv;
-    const uint8_t *live;
-    const uint32_t *live_valid;
+    GatherSrc src;
     const float *frows;
     float *bigsum;
     uint32_t nbig;             // big Gaussians, or an upper bound with nbig_dev the device's count

@@ -2,7 +2,7 @@
 // (deterministic fixed order, through the inverse permutation), then the preprocess backward of the CUDA
 // submodule restated: 2D conic -> cov2D -> cov3D -> scale / rotation, 2D mean -> 3D mean, SH -> colour.
 // Its own translation unit so it can be compiled without SLP packing (build.py FILE_FLAGS).
-#include "gsr_kernels.h"
+#include "gsr_gather.h"
 #include "gsr_sh.h"
 
 namespace gsr {
@@ -96,20 +96,16 @@ __device__ __forceinline__ void preprocess_bwd_one(const PreprocessBwdParams &p,
     if (vis && have_gs && n_tiles <= BIG_GAUSSIAN_TILES) {
 #pragma unroll
         for (int k = 0; k < 10; k++) gs[k] = gs_in[k];
-    } else if (vis && (!p.live || !*p.live_valid || p.live[i])) {  // (no non-zero row stored: zero sums)
-        const uint32_t start = p.inst_start[i], cnt = n_tiles;
+    } else if (gather_wanted(p.src, i, radius)) {  // (else no non-zero row stored: zero sums)
+        const uint32_t start = p.src.inst_start[i], cnt = n_tiles;
         if (cnt > BIG_GAUSSIAN_TILES) {
-            add_row(p.bigsum, p.big_slot[i], gs);
+            add_row(p.bigsum, p.src.big_slot[i], gs);
         } else {
             // the inv words first (INV_NONE: not loaded by the forward composite, no row), then all row loads of a
             // group, before summing (memory-level parallelism)
             for (uint32_t k0 = 0; k0 < cnt; k0 += 4) {
                 bool use[4];
-                uint32_t iv[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) iv[j] = p.inv[start + min(k0 + j, cnt - 1)];  // unconditional (clamped)
-#pragma unroll
-                for (int j = 0; j < 4; j++) use[j] = k0 + j < cnt && iv[j] != INV_NONE;
+                inv_use4(p.src, start, k0, cnt, use);
                 float rw[4][10];
 #pragma unroll
                 for (int j = 0; j < 4; j++) load_row(p.rows, use[j] ? (size_t)(start + k0 + j) : 0u, rw[j]);  // row 0: dropped
@@ -504,9 +500,9 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdParams
         float3 d3, v3;
         float cg[CAM_N] = {};
         if (i < p.g1) {
-            const int rad = p.radii[i];
+            const int rad = p.src.radii[i];
             bool zg = false;
-            preprocess_bwd_one<false, CAM>(p, cam, i, rad, rad > 0 ? p.tiles[i] : 0u, false, none, d3, v3, zg, cg);
+            preprocess_bwd_one<false, CAM>(p, cam, i, rad, rad > 0 ? p.src.tiles[i] : 0u, false, none, d3, v3, zg, cg);
         }
         if constexpr (CAM)
             cam_wave_store(cg, p.cam_partials + (size_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * CAM_SLOT, threadIdx.x & 63);
@@ -530,10 +526,10 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdParams
     {
         // radius, kept-tile count and first expansion index loaded together (clamped index, selected after)
         const int ic = min(i, p.g1 - 1);
-        const int rad_l = p.radii[ic];
-        const uint32_t cnt_l = p.tiles[ic], ist_l = p.inst_start[ic];
+        const int rad_l = p.src.radii[ic];
+        const uint32_t cnt_l = p.src.tiles[ic], ist_l = p.src.inst_start[ic];
         // no non-zero row stored (GeomState::live): the sums are zero, so its rows are not gathered
-        live = !p.live || !__builtin_amdgcn_readfirstlane(*p.live_valid) || p.live[ic] != 0;
+        live = gather_live(p.src, ic);
         rad = i < p.g1 ? rad_l : 0;
         const bool vis = rad > 0;
         cnt = vis ? cnt_l : 0u;
@@ -560,7 +556,7 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdParams
                     if (s_meta[o + step].x <= j) o += step;
                 const uint2 m = s_meta[o];
                 uu[r] = j < total ? m.y + (j - m.x) : 0u;
-                sidx[r] = p.inv[uu[r]];
+                sidx[r] = p.src.inv[uu[r]];
             }
         };
         uint32_t uu_n[PER], sidx_n[PER];
@@ -698,7 +694,7 @@ void launch_preprocess_bwd(hipStream_t s, const PreprocessBwdParams &p) {
 // Absolute screen-space sums (gsr_absgrad_ext), a kernel of its own beside preprocess_bwd_kernel so that none of that
 // kernel's forms changes: one thread per Gaussian adds its 8-B abs rows in expansion order (four inv words, then four
 // rows, in flight together), a big Gaussian takes big_reduce's sum, one without a live flag or a positive radius stays
-// zero -- the tests, and so the order of the additions, of the 40-B gather.  The statistic's norm is formed without
+// zero -- the tests (gsr_gather.h), and so the order of the additions, of the 40-B gather.  The statistic's norm is formed without
 // contraction (two products, one sum, one square root, each rounded once), so a host can reproduce its bits.
 __device__ __forceinline__ float abs_norm(float x, float y) {
 #pragma clang fp contract(off)
@@ -708,28 +704,24 @@ __device__ __forceinline__ float abs_norm(float x, float y) {
 __global__ __launch_bounds__(256) void abs_gather_kernel(AbsGatherParams p) {
     const int i = p.g0 + blockIdx.x * 256 + threadIdx.x;
     if (i >= p.g1) return;
-    const int radius = p.radii[i];
+    const int radius = p.src.radii[i];
     const bool vis = radius > 0;
     float2 st_old = make_float2(0.f, 0.f);
     if (p.densify_stats && p.densify_accumulate) st_old = *reinterpret_cast<const float2 *>(p.densify_stats + 2 * i);
     float ax = 0.f, ay = 0.f;
-    if (vis && (!p.live || !*p.live_valid || p.live[i])) {
-        const uint32_t start = p.inst_start[i], cnt = p.tiles[i];
+    if (gather_wanted(p.src, i, radius)) {
+        const uint32_t start = p.src.inst_start[i], cnt = p.src.tiles[i];
         if (cnt > BIG_GAUSSIAN_TILES) {
-            const float2 v = p.bigsum_abs[p.big_slot[i]];
+            const float2 v = p.bigsum_abs[p.src.big_slot[i]];
             ax = v.x;
             ay = v.y;
         } else {
             for (uint32_t k0 = 0; k0 < cnt; k0 += 4) {
-                uint32_t iv[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) iv[j] = p.inv[start + min(k0 + j, cnt - 1)];  // unconditional (clamped)
+                bool use[4];
+                inv_use4(p.src, start, k0, cnt, use);
                 float2 rw[4];
 #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const bool use = k0 + j < cnt && iv[j] != INV_NONE;
-                    rw[j] = use ? p.abs_rows[start + k0 + j] : make_float2(0.f, 0.f);
-                }
+                for (int j = 0; j < 4; j++) rw[j] = use[j] ? p.abs_rows[start + k0 + j] : make_float2(0.f, 0.f);
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     ax += rw[j].x;

@@ -213,16 +213,7 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
         out_invdepth=invdepth.data_ptr(), radii=radii.data_ptr())
     num_rendered = ctypes.c_int64(0)
     with torch.cuda.device(device):  # the library also switches to its stream's device (gsr_api.hip)
-        if feat is not None:
-            rc = lib.gsr_forward_features(ctypes.byref(a), None if ext is None else ctypes.byref(ext),
-                                          ctypes.byref(feat), bufs.callback, None, _stream_handle(device),
-                                          ctypes.byref(num_rendered))
-        elif ext is None:
-            rc = lib.gsr_forward(ctypes.byref(a), bufs.callback, None, _stream_handle(device),
-                                 ctypes.byref(num_rendered))
-        else:
-            rc = lib.gsr_forward_ext(ctypes.byref(a), ctypes.byref(ext), bufs.callback, None, _stream_handle(device),
-                                     ctypes.byref(num_rendered))
+        rc = _native.call_forward(lib, a, ext, feat, bufs.callback, _stream_handle(device), num_rendered)
     bufs.raise_pending()
     _native.check(rc, "rasterize_gaussians")
     state = ForwardState(means3D_c, sh_c, col_c, op_c, sc_c, rot_c, cov_c, radii, bg, view, proj, campos,
@@ -232,13 +223,66 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
     return (*res, state)
 
 
-def _alpha_grad(grad_out_alpha, H: int, W: int):
-    """The upstream gradient of alpha as a contiguous float32 (H*W) block, or None."""
-    if grad_out_alpha is None:
-        return None
-    if grad_out_alpha.numel() != H * W:
-        raise RuntimeError(f"grad_out_alpha must have shape (1, {H}, {W}), got {tuple(grad_out_alpha.shape)}")
-    return grad_out_alpha.to(torch.float32).contiguous()
+class _Upstream(NamedTuple):
+    """One backward's upstream gradients, contiguous float32 (None where absent), and what follows from them."""
+    color: torch.Tensor
+    depth: Optional[torch.Tensor]
+    alpha: Optional[torch.Tensor]
+    features: Optional[torch.Tensor]
+    bg_image: bool                         # the forward's background is a (3,H,W) image
+    ext: Optional[_native.CompositeExt]    # the backward's gsr_composite_ext, None for the plain call
+
+
+def _upstream(st: ForwardState, rs, grad_color, grad_depth, grad_alpha=None, grad_features=None, dbg=None):
+    """The upstream gradients of colour (zeros when None), inverse depth, alpha ((1,H,W) or (H,W)) and the feature image
+    ((C,H,W), only for a state with features), checked and made contiguous float32, and the call's CompositeExt: given
+    with a background image, an alpha gradient or dbg, the destination of the background's gradient."""
+    H, W = int(rs.image_height), int(rs.image_width)
+    if grad_color is None:
+        grad_color = torch.zeros(3, H, W, dtype=torch.float32, device=st.radii.device)
+    grad_color = grad_color.to(torch.float32).contiguous()
+    if grad_depth is not None:
+        grad_depth = grad_depth.to(torch.float32).contiguous()
+    if grad_alpha is not None:
+        if grad_alpha.numel() != H * W:
+            raise RuntimeError(f"grad_out_alpha must have shape (1, {H}, {W}), got {tuple(grad_alpha.shape)}")
+        grad_alpha = grad_alpha.to(torch.float32).contiguous()
+    if grad_features is not None:
+        if st.features is None:
+            raise RuntimeError("grad_out_features needs a state from forward_raw(..., features=...)")
+        C = int(st.features.shape[1])
+        if tuple(grad_features.shape) != (C, H, W):
+            raise RuntimeError(f"grad_out_features must have shape ({C}, {H}, {W}), got {tuple(grad_features.shape)}")
+        grad_features = grad_features.to(torch.float32).contiguous()
+    bg_image = _background(st.bg, H, W)
+    ext = None
+    if bg_image or grad_alpha is not None or dbg is not None:
+        ext = _native.CompositeExt(background_image=_ptr(st.bg) if bg_image else None, dL_dalpha=_ptr(grad_alpha),
+                                   dL_dbackground=None if bg_image else _ptr(dbg),
+                                   dL_dbackground_image=_ptr(dbg) if bg_image else None)
+    return _Upstream(grad_color, grad_depth, grad_alpha, grad_features, bg_image, ext)
+
+
+def _backward_args(st: ForwardState, rs, up: _Upstream, accumulate_stats, **fields):
+    """BackwardArgs with the fields every backward call shares -- the forward's inputs and buffers, the settings, the
+    upstream gradients -- and `fields`: the call's stages, range and destinations."""
+    return _native.BackwardArgs(
+        P=st.radii.shape[0], D=int(rs.sh_degree), M=st.M, W=int(rs.image_width), H=int(rs.image_height),
+        R=st.num_rendered, num_big=st.num_big, background=None if up.bg_image else _ptr(st.bg),
+        means3D=_ptr(st.means3D), colors_precomp=_ptr(st.colors_precomp), opacities=_ptr(st.opacities),
+        scales=_ptr(st.scales), scale_modifier=float(rs.scale_modifier), rotations=_ptr(st.rotations),
+        cov3D_precomp=_ptr(st.cov3D_precomp), viewmatrix=_ptr(st.viewmatrix), projmatrix=_ptr(st.projmatrix),
+        campos=_ptr(st.campos), tan_fovx=float(rs.tanfovx), tan_fovy=float(rs.tanfovy),
+        dL_dpix=up.color.data_ptr(), dL_dinvdepth=_ptr(up.depth), shs=_ptr(st.shs),
+        radii=_ptr(st.radii), geom_buffer=_ptr(st.geom_buffer), binning_buffer=_ptr(st.binning_buffer),
+        image_buffer=_ptr(st.image_buffer), antialiasing=int(bool(rs.antialiasing)), debug=int(bool(rs.debug)),
+        densify_accumulate=int(bool(accumulate_stats)), **fields)
+
+
+def _absgrad_ext(dabs: torch.Tensor, abs_stats, n: int):
+    """AbsgradExt for n Gaussians' destination dabs (n,2): an empty tensor's pointer is passed as NULL, and the library
+    then writes nothing; abs_stats counts only with a Gaussian to write."""
+    return _native.AbsgradExt(dL_dmeans2D_abs=_ptr(dabs), densify_abs=int(bool(abs_stats) and n > 0))
 
 
 def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_depth=None, out=None,
@@ -284,14 +328,6 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     device = st.radii.device  # (a scene without Gaussians keeps no means3D; its background gradients still exist)
     P = st.radii.shape[0]
     M = st.M
-    H, W = int(rs.image_height), int(rs.image_width)
-    if grad_out_color is None:
-        grad_out_color = torch.zeros(3, H, W, dtype=torch.float32, device=device)
-    grad_out_color = grad_out_color.to(torch.float32).contiguous()
-    if grad_out_depth is not None:
-        grad_out_depth = grad_out_depth.to(torch.float32).contiguous()
-    grad_out_alpha = _alpha_grad(grad_out_alpha, H, W)
-    bg_image = _background(st.bg, H, W)
     f32 = dict(dtype=torch.float32, device=device)
     out = out or {}
 
@@ -323,58 +359,27 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     dproj = dst("projmatrix", 4, 4) if camera_grads else None
     dcampos = dst("campos", 3) if camera_grads else None
     dbg = dst("bg", *st.bg.shape) if (background_grad or "bg" in out) else None
+    up = _upstream(st, rs, grad_out_color, grad_out_depth, grad_out_alpha, grad_out_features, dbg)
     feat = dfeat = None
     if st.features is not None:
         C = int(st.features.shape[1])
-        if grad_out_features is not None:
-            if tuple(grad_out_features.shape) != (C, H, W):
-                raise RuntimeError(f"grad_out_features must have shape ({C}, {H}, {W}), got "
-                                   f"{tuple(grad_out_features.shape)}")
-            grad_out_features = grad_out_features.to(torch.float32).contiguous()
         dfeat = dst("features", P, C)
-        feat = _native.FeaturesExt(C=C, features=_ptr(st.features), dL_dout_features=_ptr(grad_out_features),
+        feat = _native.FeaturesExt(C=C, features=_ptr(st.features), dL_dout_features=_ptr(up.features),
                                    dL_dfeatures=_ptr(dfeat))
-    elif grad_out_features is not None:
-        raise RuntimeError("grad_out_features needs a state from forward_raw(..., features=...)")
-    ext = None
-    if bg_image or grad_out_alpha is not None or dbg is not None:
-        ext = _native.CompositeExt(background_image=_ptr(st.bg) if bg_image else None, dL_dalpha=_ptr(grad_out_alpha),
-                                   dL_dbackground=None if bg_image else _ptr(dbg),
-                                   dL_dbackground_image=_ptr(dbg) if bg_image else None)
+    # (features with absgrad: refused by the library, GSR_ERR_UNSUPPORTED -> NotImplementedError)
+    ab = None if dabs is None else _absgrad_ext(dabs, abs_stats, P)
     bufs = _Buffers(device)
-    a = _native.BackwardArgs(
-        P=P, D=int(rs.sh_degree), M=M, W=W, H=H, R=st.num_rendered, num_big=st.num_big,
-        background=None if bg_image else _ptr(st.bg),
-        means3D=_ptr(st.means3D), colors_precomp=_ptr(st.colors_precomp), opacities=_ptr(st.opacities),
-        scales=_ptr(st.scales), scale_modifier=float(rs.scale_modifier), rotations=_ptr(st.rotations),
-        cov3D_precomp=_ptr(st.cov3D_precomp), viewmatrix=_ptr(st.viewmatrix), projmatrix=_ptr(st.projmatrix),
-        campos=_ptr(st.campos), tan_fovx=float(rs.tanfovx), tan_fovy=float(rs.tanfovy),
-        dL_dpix=grad_out_color.data_ptr(), dL_dinvdepth=_ptr(grad_out_depth), shs=_ptr(st.shs),
-        radii=_ptr(st.radii), geom_buffer=_ptr(st.geom_buffer), binning_buffer=_ptr(st.binning_buffer),
-        image_buffer=_ptr(st.image_buffer), antialiasing=int(bool(rs.antialiasing)), debug=int(bool(rs.debug)),
+    a = _backward_args(
+        st, rs, up, accumulate_stats,
         dL_dmeans2D=dmeans2D.data_ptr(), dL_dcolors=_ptr(dcolors), dL_dopacity=dopac.data_ptr(),
         dL_dmeans3D=dmeans3D.data_ptr(), dL_dcov3D=_ptr(dcov), dL_dsh=_ptr(dsh),
         dL_dscales=dscales.data_ptr(), dL_drotations=drot.data_ptr(), dL_dcolors_sh=_ptr(dcsh),
-        densify_stats=_ptr(dstats), densify_accumulate=int(bool(accumulate_stats)), max_radii2D=_ptr(mrad),
+        densify_stats=_ptr(dstats), max_radii2D=_ptr(mrad),
         campos_rows=cam_rows, campos_rank=cam_rank, campos_nrows=cam_n,
         dL_dviewmatrix=_ptr(dview), dL_dprojmatrix=_ptr(dproj), dL_dcampos=_ptr(dcampos))
     with torch.cuda.device(device):
-        if feat is not None:
-            ab = None
-            if dabs is not None:  # (refused by the library: GSR_ERR_UNSUPPORTED -> NotImplementedError)
-                ab = _native.AbsgradExt(dL_dmeans2D_abs=dabs.data_ptr(), densify_abs=int(bool(abs_stats) and P > 0))
-            rc = lib.gsr_backward_features(ctypes.byref(a), None if ext is None else ctypes.byref(ext),
-                                           None if ab is None else ctypes.byref(ab), ctypes.byref(feat),
-                                           bufs.callback, None, _stream_handle(device))
-        elif dabs is not None:
-            # (P == 0: the pointer of an empty tensor is passed as NULL and the library writes nothing)
-            ab = _native.AbsgradExt(dL_dmeans2D_abs=_ptr(dabs), densify_abs=int(bool(abs_stats) and P > 0))
-            rc = lib.gsr_backward_abs(ctypes.byref(a), None if ext is None else ctypes.byref(ext), ctypes.byref(ab),
-                                      bufs.callback, None, _stream_handle(device))
-        elif ext is None:
-            rc = lib.gsr_backward(ctypes.byref(a), bufs.callback, None, _stream_handle(device))
-        else:
-            rc = lib.gsr_backward_ext(ctypes.byref(a), ctypes.byref(ext), bufs.callback, None, _stream_handle(device))
+        rc = _native.call_backward(lib, a, ext=up.ext, absgrad=ab, feat=feat, cb=bufs.callback,
+                                   stream=_stream_handle(device))
     bufs.raise_pending()
     _native.check(rc, "rasterize_gaussians_backward")
     camera = dict(viewmatrix=dview, projmatrix=dproj, campos=dcampos) if camera_grads else {}
@@ -423,23 +428,12 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
         raise NotImplementedError("backward_chunked: a forward state with features needs backward_raw (the split "
                                   "backward of feature channels is not built)")
     device = st.radii.device  # (as backward_raw: a scene without Gaussians keeps no means3D)
-    P, M = st.radii.shape[0], st.M
-    H, W = int(rs.image_height), int(rs.image_width)
-    if grad_out_color is None:
-        grad_out_color = torch.zeros(3, H, W, dtype=torch.float32, device=device)
-    grad_out_color = grad_out_color.to(torch.float32).contiguous()
-    if grad_out_depth is not None:
-        grad_out_depth = grad_out_depth.to(torch.float32).contiguous()
-    grad_out_alpha = _alpha_grad(grad_out_alpha, H, W)
-    bg_image = _background(st.bg, H, W)
-    ext = None  # (the per-Gaussian calls take it too: with a background image there is no background vector)
+    M = st.M
     if bg_out is not None and (tuple(bg_out.shape) != tuple(st.bg.shape) or bg_out.dtype != torch.float32
                                or not bg_out.is_contiguous()):
         raise RuntimeError(f"bg_out must be a contiguous float32 tensor of shape {tuple(st.bg.shape)}")
-    if bg_image or grad_out_alpha is not None or bg_out is not None:
-        ext = _native.CompositeExt(background_image=_ptr(st.bg) if bg_image else None, dL_dalpha=_ptr(grad_out_alpha),
-                                   dL_dbackground=None if bg_image else _ptr(bg_out),
-                                   dL_dbackground_image=_ptr(bg_out) if bg_image else None)
+    # (the per-Gaussian calls take up.ext too: with a background image there is no background vector)
+    up = _upstream(st, rs, grad_out_color, grad_out_depth, grad_out_alpha, dbg=bg_out)
 
     chunks = list(chunks)
     with_abs = [("means2D_abs" in out) for _, _, out in chunks]
@@ -449,31 +443,16 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
         raise RuntimeError("abs_stats=True needs out['means2D_abs'] and out['densify_stats'] in every chunk")
 
     def call(a, ab=None):
-        if ab is not None:
-            return lib.gsr_backward_abs(ctypes.byref(a), None if ext is None else ctypes.byref(ext), ctypes.byref(ab),
-                                        bufs.callback, None, _stream_handle(device))
-        if ext is None:
-            return lib.gsr_backward(ctypes.byref(a), bufs.callback, None, _stream_handle(device))
-        return lib.gsr_backward_ext(ctypes.byref(a), ctypes.byref(ext), bufs.callback, None, _stream_handle(device))
+        return _native.call_backward(lib, a, ext=up.ext, absgrad=ab, feat=None, cb=bufs.callback,
+                                     stream=_stream_handle(device))
 
     bufs = _Buffers(device)
-    base = dict(
-        P=P, D=int(rs.sh_degree), M=M, W=W, H=H, R=st.num_rendered, num_big=st.num_big,
-        background=None if bg_image else _ptr(st.bg),
-        means3D=_ptr(st.means3D), colors_precomp=_ptr(st.colors_precomp), opacities=_ptr(st.opacities),
-        scales=_ptr(st.scales), scale_modifier=float(rs.scale_modifier), rotations=_ptr(st.rotations),
-        cov3D_precomp=_ptr(st.cov3D_precomp), viewmatrix=_ptr(st.viewmatrix), projmatrix=_ptr(st.projmatrix),
-        campos=_ptr(st.campos), tan_fovx=float(rs.tanfovx), tan_fovy=float(rs.tanfovy),
-        dL_dpix=grad_out_color.data_ptr(), dL_dinvdepth=_ptr(grad_out_depth), shs=_ptr(st.shs),
-        radii=_ptr(st.radii), geom_buffer=_ptr(st.geom_buffer), binning_buffer=_ptr(st.binning_buffer),
-        image_buffer=_ptr(st.image_buffer), antialiasing=int(bool(rs.antialiasing)), debug=int(bool(rs.debug)),
-        densify_accumulate=int(bool(accumulate_stats)))
     with torch.cuda.device(device):
-        a = _native.BackwardArgs(stages=_native.GSR_BWD_COMPOSITE, **base)
+        a = _backward_args(st, rs, up, accumulate_stats, stages=_native.GSR_BWD_COMPOSITE)
         # (the compositing call does not write through the pointer: non-NULL asks for the abs rows)
         want_abs = any(with_abs) and any(out["means2D_abs"].numel() for _, _, out in chunks)
-        rc = call(a, _native.AbsgradExt(dL_dmeans2D_abs=next(
-            _ptr(out["means2D_abs"]) for _, _, out in chunks if out["means2D_abs"].numel())) if want_abs else None)
+        rc = call(a, _absgrad_ext(next(out["means2D_abs"] for _, _, out in chunks if out["means2D_abs"].numel()),
+                                  False, 0) if want_abs else None)
         bufs.raise_pending()
         _native.check(rc, "rasterize_gaussians_backward (composite)")
         scratch = bufs.get(_native.GSR_BUF_BWD_SCRATCH)
@@ -498,8 +477,8 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
                     raise RuntimeError(f"chunk {k}: out[{name!r}] must be a contiguous {want[0]} tensor of {n} rows")
             if compact_sh and "colors_sh" not in out and st.shs is not None:
                 raise RuntimeError("compact_sh needs out['colors_sh'] in every chunk")
-            a = _native.BackwardArgs(
-                stages=_native.GSR_BWD_GAUSSIANS, g_begin=int(g0), g_end=int(g1), bwd_scratch=_ptr(scratch),
+            a = _backward_args(
+                st, rs, up, accumulate_stats, stages=_native.GSR_BWD_GAUSSIANS, g_begin=int(g0), g_end=int(g1), bwd_scratch=_ptr(scratch),
                 dL_dmeans2D=_ptr(out.get("means2D")), dL_dcolors=_ptr(out.get("colors")),
                 dL_dopacity=_ptr(out.get("opacities")), dL_dmeans3D=_ptr(out.get("means3D")),
                 dL_dcov3D=_ptr(out.get("cov3D")), dL_dsh=None if compact_sh else _ptr(out.get("shs")),
@@ -507,12 +486,8 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
                 dL_dcolors_sh=_ptr(out.get("colors_sh")), densify_stats=_ptr(out.get("densify_stats")),
                 max_radii2D=_ptr(out.get("max_radii2D")), campos_rows=cam_rows, campos_rank=cam_rank,
                 campos_nrows=cam_n, dL_dviewmatrix=_ptr(out.get("viewmatrix")),
-                dL_dprojmatrix=_ptr(out.get("projmatrix")), dL_dcampos=_ptr(out.get("campos")), **base)
-            ab = None
-            if want_abs:
-                ab = _native.AbsgradExt(dL_dmeans2D_abs=_ptr(out["means2D_abs"]),
-                                        densify_abs=int(bool(abs_stats) and n > 0))
-            rc = call(a, ab)
+                dL_dprojmatrix=_ptr(out.get("projmatrix")), dL_dcampos=_ptr(out.get("campos")))
+            rc = call(a, _absgrad_ext(out["means2D_abs"], abs_stats, n) if want_abs else None)
             bufs.raise_pending()
             _native.check(rc, f"rasterize_gaussians_backward (chunk {k})")
             if on_chunk is not None:
@@ -535,91 +510,67 @@ def _campos_rows(spec):
     return rows.data_ptr(), int(rank), int(rows.shape[0])
 
 
+def _save_state(ctx, st: ForwardState):
+    """Keep a ForwardState on an autograd context: its tensors saved (an empty one in place of None), the rest plain."""
+    tensors = st[:15] + (() if st.features is None else (st.features,))
+    ctx.meta = (st.num_rendered, st.num_big, st.M)
+    ctx.present = tuple(t is not None for t in tensors)
+    empty = torch.empty(0, device=st.radii.device)
+    ctx.save_for_backward(*[(t if t is not None else empty) for t in tensors])
+
+
+def _saved_state(ctx) -> ForwardState:
+    tensors = [t if present else None for t, present in zip(ctx.saved_tensors, ctx.present)]
+    return ForwardState(*tensors[:15], *ctx.meta, *tensors[15:])
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, return_alpha=False, absgrad=False, bg=None, *camera):
-        # bg: None or the settings' bg once more, camera: () or the settings' (viewmatrix, projmatrix, campos) once
-        # more, as inputs autograd can hand a gradient to (rasterize_gaussians); the values are read from the settings
-        # either way
+                raster_settings, flags=(False, False), features=None, bg=None, *camera):
+        # flags: (return_alpha, absgrad).  features: None or the (P,C) channels.  bg: None or the settings' bg once
+        # more, camera: () or the settings' (viewmatrix, projmatrix, campos) once more, as inputs autograd can hand a
+        # gradient to (rasterize_gaussians); the values are read from the settings either way
+        return_alpha, absgrad = flags
         res = forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                          return_alpha=return_alpha)
-        st = res[-1]
+                          return_alpha=return_alpha, features=features)
         ctx.raster_settings = raster_settings
+        ctx.return_alpha = bool(return_alpha)
         # absgrad: the backward sets means2D.absgrad on the caller's tensor (as gsplat's does)
         ctx.absgrad_of = means2D if (absgrad and torch.is_tensor(means2D)) else None
         ctx.bg = None if bg is None else (tuple(bg.shape), bg.device)
         ctx.camera = [(tuple(t.shape), t.device) for t in camera]
-        ctx.meta = (st.num_rendered, st.num_big, st.M)
-        ctx.present = tuple(t is not None for t in st)
-        empty = torch.empty(0, device=means3D.device)
-        ctx.save_for_backward(*[(t if t is not None else empty) for t in st[:15]])
+        _save_state(ctx, res[-1])
         ctx.set_materialize_grads(False)
-        return res[:-1]  # (color, radii, invdepth) or (color, radii, invdepth, alpha)
-
-    @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, grad_out_alpha=None):
-        saved = ctx.saved_tensors
-        tensors = [t if present else None for t, present in zip(saved, ctx.present[:15])]
-        st = ForwardState(*tensors, *ctx.meta)
-        need = ctx.needs_input_grad
-        g = backward_raw(st, ctx.raster_settings, grad_out_color, grad_out_depth, camera_grads=any(need[12:]),
-                         grad_out_alpha=grad_out_alpha, background_grad=need[11], absgrad=ctx.absgrad_of is not None)
-        if ctx.absgrad_of is not None:  # (P,3) with z = 0, so code that takes [:, :2] of means2D.grad works on it
-            m2a = g["means2D_abs"]
-            ctx.absgrad_of.absgrad = torch.cat([m2a, m2a.new_zeros(m2a.shape[0], 1)], dim=1)
-        return _input_grads(ctx, g, need)
-
-
-def _input_grads(ctx, g, need):
-    """backward_raw's result as the gradients of _RasterizeGaussians.forward's inputs (need: their needs_input_grad)."""
-    camera = tuple(g[name].reshape(shape).to(dev) if wanted else None for name, (shape, dev), wanted in
-                   zip(("viewmatrix", "projmatrix", "campos"), ctx.camera, need[12:]))
-    camera = (None, None, g["bg"].reshape(ctx.bg[0]).to(ctx.bg[1]) if need[11] else None) + camera
-    return (g["means3D"] if need[0] else None,
-            g["means2D"] if need[1] else None,
-            g["shs"] if need[2] else None,
-            g["colors_precomp"] if need[3] else None,
-            g["opacities"] if need[4] else None,
-            g["scales"] if need[5] else None,
-            g["rotations"] if need[6] else None,
-            g["cov3D_precomp"] if need[7] else None,
-            None, *camera)
-
-
-class _RasterizeGaussiansFeatures(torch.autograd.Function):
-    """_RasterizeGaussians with feature channels, a function of its own so that the call without features stays what
-    it is: features is the first input, the feature image (C,H,W) the last output."""
-
-    @staticmethod
-    def forward(ctx, features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, return_alpha=False, bg=None, *camera):
-        res = forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                          return_alpha=return_alpha, features=features)
-        st = res[-1]
-        ctx.raster_settings = raster_settings
-        ctx.return_alpha = bool(return_alpha)
-        ctx.bg = None if bg is None else (tuple(bg.shape), bg.device)
-        ctx.camera = [(tuple(t.shape), t.device) for t in camera]
-        ctx.meta = (st.num_rendered, st.num_big, st.M)
-        ctx.present = tuple(t is not None for t in st)
-        empty = torch.empty(0, device=means3D.device)
-        ctx.save_for_backward(*[(t if t is not None else empty) for t in st[:15]], st.features)
-        ctx.set_materialize_grads(False)
-        return res[:-1]  # (color, radii, invdepth[, alpha], feature_image)
+        return res[:-1]  # (color, radii, invdepth[, alpha][, feature_image])
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, *rest):
-        grad_out_alpha, grad_out_features = rest if ctx.return_alpha else (None, rest[0])
-        saved = ctx.saved_tensors
-        tensors = [t if present else None for t, present in zip(saved[:15], ctx.present[:15])]
-        st = ForwardState(*tensors, *ctx.meta, saved[15])
-        need = ctx.needs_input_grad[1:]  # as _RasterizeGaussians' inputs, but for absgrad (index 10, a flag)
-        need = need[:10] + (False,) + need[10:]
+        st = _saved_state(ctx)
+        rest = list(rest)
+        grad_out_alpha = rest.pop(0) if ctx.return_alpha else None
+        grad_out_features = rest.pop(0) if st.features is not None else None
+        need = ctx.needs_input_grad
         g = backward_raw(st, ctx.raster_settings, grad_out_color, grad_out_depth, camera_grads=any(need[12:]),
-                         grad_out_alpha=grad_out_alpha, background_grad=need[11], grad_out_features=grad_out_features)
-        grads = _input_grads(ctx, g, need)
-        return (g["features"] if ctx.needs_input_grad[0] else None, *grads[:10], *grads[11:])
+                         grad_out_alpha=grad_out_alpha, background_grad=need[11], absgrad=ctx.absgrad_of is not None,
+                         grad_out_features=grad_out_features)
+        if ctx.absgrad_of is not None:  # (P,3) with z = 0, so code that takes [:, :2] of means2D.grad works on it
+            m2a = g["means2D_abs"]
+            ctx.absgrad_of.absgrad = torch.cat([m2a, m2a.new_zeros(m2a.shape[0], 1)], dim=1)
+        camera = tuple(g[name].reshape(shape).to(dev) if wanted else None for name, (shape, dev), wanted in
+                       zip(("viewmatrix", "projmatrix", "campos"), ctx.camera, need[12:]))
+        return (g["means3D"] if need[0] else None,
+                g["means2D"] if need[1] else None,
+                g["shs"] if need[2] else None,
+                g["colors_precomp"] if need[3] else None,
+                g["opacities"] if need[4] else None,
+                g["scales"] if need[5] else None,
+                g["rotations"] if need[6] else None,
+                g["cov3D_precomp"] if need[7] else None,
+                None, None,  # raster_settings, flags
+                g["features"] if need[10] else None,
+                g["bg"].reshape(ctx.bg[0]).to(ctx.bg[1]) if need[11] else None,
+                *camera)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -647,12 +598,9 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
             and any(t.requires_grad for t in camera)):
         camera = ()  # the call as it is without camera gradients
     bg = rs.bg if (torch.is_grad_enabled() and torch.is_tensor(rs.bg) and rs.bg.requires_grad) else None
-    if features is not None:
-        return _RasterizeGaussiansFeatures.apply(features, means3D, means2D, sh, colors_precomp, opacities, scales,
-                                                 rotations, cov3Ds_precomp, raster_settings, bool(return_alpha), bg,
-                                                 *camera)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, bool(return_alpha), bool(absgrad), bg, *camera)
+                                     cov3Ds_precomp, raster_settings, (bool(return_alpha), bool(absgrad)), features, bg,
+                                     *camera)
 
 
 def sh_backward_views(means3D: torch.Tensor, campos: torch.Tensor, dcolors_sh: torch.Tensor, sh_degree: int, M: int,
@@ -723,9 +671,7 @@ class GaussianRasterizer(nn.Module):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-        if features is not None:  # (color, radii, invdepth[, alpha], feature_image (C,H,W)): rasterize_gaussians
-            return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, rs, return_alpha=self.return_alpha, absgrad=self.absgrad,
-                                       features=features)
+        # (color, radii, invdepth[, alpha][, feature_image (C,H,W)]): rasterize_gaussians
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, rs, return_alpha=self.return_alpha, absgrad=self.absgrad)
+                                   cov3D_precomp, rs, return_alpha=self.return_alpha, absgrad=self.absgrad,
+                                   features=features)

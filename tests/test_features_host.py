@@ -55,6 +55,10 @@ def test_scratch_size_arithmetic():
     for R, nb in ((0, 0), (1000, 10), (123457, 3), (4_200_000, 1500)):
         base = up(max(R, 1) * 40) + up(max(nb, 1) * 40) + 256
         assert lib.gsr_bwd_scratch_bytes(R, nb) == base  # the plain layout is unchanged
+        # the abs layout and the feature layout both start with the plain layout: each is the plain size, which keeps
+        # what follows 256-B aligned, plus its own per-instance and per-big-Gaussian rows
+        assert base % 256 == 0
+        assert lib.gsr_bwd_scratch_bytes_abs(R, nb) == base + up(max(R, 1) * 8) + up(max(nb, 1) * 8)
         for C in (1, 3, 7, 8, 9, 16, 17, 33, 64):
             B = 8 if C <= 8 else 16  # one channel block's rows, whatever C is
             assert lib.gsr_bwd_scratch_bytes_features(R, nb, C) == base + up(max(R, 1) * B * 4) + up(max(nb, 1) * B * 4)

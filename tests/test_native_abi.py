@@ -101,3 +101,59 @@ def test_python_api_mirrors_upstream():
     with pytest.raises(RuntimeError, match="HIP device"):
         r(means3D=x, means2D=x, opacities=torch.zeros(4, 1), shs=torch.zeros(4, 1, 3), scales=x,
           rotations=torch.zeros(4, 4))
+
+
+class _RecordingLib:
+    """Stands in for the loaded library: every gsr_* attribute is a function that records its name and arguments."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        if not name.startswith("gsr_"):
+            raise AttributeError(name)
+
+        def entry(*args):
+            self.calls.append((name, args))
+            return 0
+
+        return entry
+
+
+def test_dispatchers_pick_the_narrowest_entry_point():
+    """call_forward / call_backward reach the entry point with no more side structs than were given -- all None is
+    the plain gsr_forward / gsr_backward -- and look it up on the library object at call time."""
+    E, A, F = _native.CompositeExt(), _native.AbsgradExt(), _native.FeaturesExt(C=3)
+    fa, ba, num = _native.ForwardArgs(), _native.BackwardArgs(), ctypes.c_int64(0)
+    for ext in (None, E):
+        for feat in (None, F):
+            lib = _RecordingLib()
+            assert _native.call_forward(lib, fa, ext, feat, None, None, num) == 0
+            want = "gsr_forward_features" if feat is not None else "gsr_forward_ext" if ext is not None else "gsr_forward"
+            (name, args), = lib.calls
+            assert name == want, (ext, feat)
+            # the args struct first, then the given side structs in the C order, NULL for an absent one in between
+            assert len(args) == 5 + (want != "gsr_forward") + (want == "gsr_forward_features")
+            if want == "gsr_forward_features":
+                assert (args[1] is None) == (ext is None) and args[2] is not None
+            for absgrad in (None, A):
+                lib = _RecordingLib()
+                assert _native.call_backward(lib, ba, ext, absgrad, feat, None, None) == 0
+                want = ("gsr_backward_features" if feat is not None else "gsr_backward_abs" if absgrad is not None
+                        else "gsr_backward_ext" if ext is not None else "gsr_backward")
+                (name, args), = lib.calls
+                assert name == want, (ext, absgrad, feat)
+                assert len(args) == 4 + ("gsr_backward", "gsr_backward_ext", "gsr_backward_abs",
+                                         "gsr_backward_features").index(want)
+                if want in ("gsr_backward_abs", "gsr_backward_features"):
+                    assert (args[1] is None) == (ext is None)
+                if want == "gsr_backward_features":
+                    assert (args[2] is None) == (absgrad is None)
+    # looked up at call time: an attribute patched onto the object is what runs
+    lib = _RecordingLib()
+    lib.gsr_forward = lambda *args: 41
+    lib.gsr_backward = lambda *args: 42
+    assert _native.call_forward(lib, fa, None, None, None, None, num) == 41
+    assert _native.call_backward(lib, ba, None, None, None, None, None) == 42
+    assert lib.calls == []
+    assert _native.call_forward(lib, fa, E, None, None, None, num) == 0 and lib.calls[-1][0] == "gsr_forward_ext"
