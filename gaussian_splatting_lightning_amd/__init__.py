@@ -5,6 +5,7 @@ backward -- runs in hand-written HIP kernels for gfx950 (csrc/), exposed through
 include/gsrast.h and bound here with ctypes.  See DESIGN.md.
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, mark_visible,  # noqa: F401
-                         rasterize_gaussians)
+                         rasterize_contributions, rasterize_gaussians)
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "mark_visible"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_contributions",
+           "mark_visible"]

@@ -78,6 +78,17 @@ class FeaturesExt(ctypes.Structure):  # include/gsrast.h gsr_features_ext (versi
 
 
 FEATURES_MAX_C = 64  # include/gsrast.h gsr_features_ext.C
+GSR_BUF_CONTRIB_SCRATCH = 6
+
+
+class ContribArgs(ctypes.Structure):  # include/gsrast.h gsr_contrib_args (versioned by struct_size)
+    _fields_ = [("struct_size", ctypes.c_size_t), ("P", ctypes.c_int), ("W", ctypes.c_int), ("H", ctypes.c_int),
+                ("R", ctypes.c_int64), ("num_big", ctypes.c_int64), ("radii", _fp), ("geom_buffer", _fp),
+                ("binning_buffer", _fp), ("image_buffer", _fp), ("pixel_weights", _fp), ("count", _fp), ("wsum", _fp),
+                ("wmax", _fp), ("accumulate", ctypes.c_int)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=ctypes.sizeof(ContribArgs), **fields)
 
 
 class AdamGroup(ctypes.Structure):
@@ -144,6 +155,7 @@ EXPORTED_SYMBOLS = (
     "gsr_knn_workspace_bytes", "gsr_knn_mean_dist2", "gsr_debug_wave_stamps",
     "gsr_forward_ext", "gsr_backward_ext", "gsr_backward_abs", "gsr_bwd_scratch_bytes_abs",
     "gsr_forward_features", "gsr_backward_features", "gsr_bwd_scratch_bytes_features",
+    "gsr_contributions", "gsr_contrib_scratch_bytes", "gsr_densify_classify_keep",
 )
 
 _lib = None
@@ -189,6 +201,14 @@ def load(path: str | None = None):
         lib.gsr_backward_features.restype = ctypes.c_int
         lib.gsr_bwd_scratch_bytes_features.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
         lib.gsr_bwd_scratch_bytes_features.restype = ctypes.c_size_t
+    if hasattr(lib, "gsr_contributions"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
+        lib.gsr_contributions.argtypes = [ctypes.POINTER(ContribArgs), ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p]
+        lib.gsr_contributions.restype = ctypes.c_int
+        lib.gsr_contrib_scratch_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64]
+        lib.gsr_contrib_scratch_bytes.restype = ctypes.c_size_t
+        lib.gsr_densify_classify_keep.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p]
+        lib.gsr_densify_classify_keep.restype = ctypes.c_int
     lib.gsr_mark_visible.argtypes = [ctypes.c_int, _fp, _fp, _fp, _fp, ctypes.c_void_p]
     lib.gsr_mark_visible.restype = ctypes.c_int
     lib.gsr_sh_backward_views.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp,
@@ -311,6 +331,11 @@ def call_backward(lib, args, ext, absgrad, feat, cb, stream) -> int:
     if ext is not None:
         return lib.gsr_backward_ext(a, ctypes.byref(ext), cb, None, stream)
     return lib.gsr_backward(a, cb, None, stream)
+
+
+def call_contributions(lib, args, cb, stream) -> int:
+    """gsr_contributions (args: ContribArgs), looked up on `lib` at call time like the two above."""
+    return lib.gsr_contributions(ctypes.byref(args), cb, None, stream)
 
 
 def check(rc: int, what: str) -> None:

@@ -85,13 +85,16 @@ enum Stage {
     ST_FEAT_FWD,
     ST_FEAT_BWD,
     ST_FEAT_GATHER,
+    ST_CONTRIB_WALK,
+    ST_CONTRIB_GATHER,
     ST_COUNT
 };
 const char *kStageNames[ST_COUNT] = {"preprocess", "depth_sort", "instance_scan", "readback",
                                      "expand",     "tile_sort",  "tile_ranges",   "render_fwd",
                                      "render_bwd", "big_reduce", "preprocess_bwd", "sh_views",
                                      "bucket_count", "bucket_scatter", "seg_sort", "adam_sh_views",
-                                     "background_grad", "feat_fwd", "feat_bwd", "feat_gather"};
+                                     "background_grad", "feat_fwd", "feat_bwd", "feat_gather",
+                                     "contrib_walk", "contrib_gather"};
 
 struct Profiler {
     std::mutex mu;
@@ -466,6 +469,22 @@ size_t gsr_bwd_scratch_bytes(int64_t R, int64_t num_big) { return bwd_scratch_si
 size_t gsr_bwd_scratch_bytes_abs(int64_t R, int64_t num_big) { return bwd_scratch_size(R, num_big, true, 0); }
 size_t gsr_bwd_scratch_bytes_features(int64_t R, int64_t num_big, int C) {
     return (C < 1 || C > FEAT_MAX_C) ? 0 : bwd_scratch_size(R, num_big, false, feat_block(C));
+}
+
+// gsr_contributions' scratch: one 16-B row per instance, then one per big Gaussian (num_big < 0: the most there can
+// be, as the backward sizes its sums).  A null base returns the size only.
+static size_t carve_contrib_scratch(char *base, int64_t R, int64_t num_big, uint4 **rows, uint4 **bigsum) {
+    if (R < 0) R = 0;
+    const int64_t nbig = num_big < 0 ? R / (BIG_GAUSSIAN_TILES + 1) + 1 : num_big;
+    Carver c(base);
+    uint4 *r = c.take<uint4>((size_t)(R ? R : 1));
+    uint4 *b = c.take<uint4>((size_t)(nbig ? nbig : 1));
+    if (rows) *rows = r;
+    if (bigsum) *bigsum = b;
+    return align_up(c.off, 256);
+}
+size_t gsr_contrib_scratch_bytes(int64_t R, int64_t num_big) {
+    return carve_contrib_scratch(nullptr, R, num_big, nullptr, nullptr);
 }
 
 void gsr_state_layout_query(int P, int64_t R, int W, int H, gsr_state_layout *caller) {
@@ -1220,6 +1239,70 @@ int gsr_backward_features(const gsr_backward_args *a, const gsr_composite_ext *e
     return bwd_gaussians(c);
 }
 
+int gsr_contributions(const gsr_contrib_args *x, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr) {
+    if (!x || !alloc) return fail(GSR_ERR_ARG, "null argument");
+    const VersionedIn<gsr_contrib_args> in(x);
+    if (!in.covers(&gsr_contrib_args::radii))
+        return fail(GSR_ERR_ARG, "gsr_contrib_args: struct_size ends before the first pointer field");
+    const int P = in.get(&gsr_contrib_args::P), W = in.get(&gsr_contrib_args::W), H = in.get(&gsr_contrib_args::H);
+    const int64_t R = in.get(&gsr_contrib_args::R), num_big = in.get(&gsr_contrib_args::num_big);
+    const int32_t *radii = in.get(&gsr_contrib_args::radii);
+    const void *geom = in.get(&gsr_contrib_args::geom_buffer), *binning = in.get(&gsr_contrib_args::binning_buffer);
+    const void *image = in.get(&gsr_contrib_args::image_buffer);
+    int64_t *count = in.get(&gsr_contrib_args::count);
+    float *wsum = in.get(&gsr_contrib_args::wsum), *wmax = in.get(&gsr_contrib_args::wmax);
+    const int accumulate = in.get(&gsr_contrib_args::accumulate);
+    if (!count && !wsum && !wmax) return fail(GSR_ERR_ARG, "gsr_contributions: no output asked for");
+    if (P < 0) return fail(GSR_ERR_ARG, "P must be >= 0");
+    if (W <= 0 || H <= 0) return fail(GSR_ERR_ARG, "image_width and image_height must be positive");
+    if ((int64_t)W * H > 0x7fffffffLL) return fail(GSR_ERR_ARG, "image too large");
+    if (R < 0 || R > 0xffffffffLL) return fail(GSR_ERR_ARG, "bad num_rendered");
+    if (num_big > P) return fail(GSR_ERR_ARG, "bad num_big");
+    if (R > 0 && (!radii || !geom || !binning || !image)) return fail(GSR_ERR_ARG, "forward buffers are required");
+    if (P == 0) return GSR_OK;
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    StreamDeviceGuard device_guard(stream);
+    if (R == 0) {  // everything culled: the empty reductions (nothing to add under accumulate)
+        if (accumulate) return GSR_OK;
+        if (count) GSR_HIP(hipMemsetAsync(count, 0, sizeof(int64_t) * (size_t)P, stream));
+        if (wsum) GSR_HIP(hipMemsetAsync(wsum, 0, sizeof(float) * (size_t)P, stream));
+        if (wmax) GSR_HIP(hipMemsetAsync(wmax, 0, sizeof(float) * (size_t)P, stream));
+        return GSR_OK;
+    }
+    const int gx = (W + BLOCK_X - 1) / BLOCK_X, gy = (H + BLOCK_Y - 1) / BLOCK_Y;
+    const uint32_t T = (uint32_t)(gx * gy);
+    GeomState g;
+    BinningState b;
+    ImageState im;
+    carve_geom(static_cast<char *>(const_cast<void *>(geom)), P, g);
+    carve_binning(static_cast<char *>(const_cast<void *>(binning)), R, T, b);
+    carve_image(static_cast<char *>(const_cast<void *>(image)), W, H, im);
+    char *scratch = alloc(alloc_ctx, GSR_BUF_CONTRIB_SCRATCH, gsr_contrib_scratch_bytes(R, num_big));
+    if (!scratch) return fail(GSR_ERR_ALLOC, "contribution scratch allocation failed");
+    uint4 *rows, *bigsum;
+    carve_contrib_scratch(scratch, R, num_big, &rows, &bigsum);
+    ContribWalkParams wp;
+    wp.W = W; wp.H = H; wp.gx = gx; wp.gy = gy; wp.num_tiles = (int)T;
+    wp.ranges = im.ranges; wp.point_list = b.point_list; wp.n_contrib = im.n_contrib;
+    wp.tile_last = im.tile_last; wp.tile_loaded = im.tile_loaded; wp.sorted_u = b.sorted_u;
+    wp.rec = g.rec; wp.pixel_weights = in.get(&gsr_contrib_args::pixel_weights); wp.rows = rows; wp.strip_exact = 1;
+    ContribGatherParams gp;
+    gp.P = P;
+    gp.src.radii = radii; gp.src.tiles = g.tiles; gp.src.inst_start = g.inst_start;
+    gp.src.big_slot = g.big_slot; gp.src.big_list = g.big_list; gp.src.inv = b.inv;
+    gp.src.live = nullptr; gp.src.live_valid = nullptr;  // the backward composite's: not valid here
+    gp.rows = rows; gp.bigsum = bigsum;
+    gp.nbig = num_big < 0 ? (uint32_t)(R / (BIG_GAUSSIAN_TILES + 1) + 1) : (uint32_t)num_big;
+    gp.nbig_dev = num_big < 0 ? g.counters + CNT_BIG : nullptr;
+    gp.count = count; gp.wsum = wsum; gp.wmax = wmax; gp.accumulate = accumulate;
+    GSR_STAGE(ST_CONTRIB_WALK, false, launch_contrib_walk(stream, wp));
+    GSR_STAGE(ST_CONTRIB_GATHER, false, {
+        launch_contrib_big_reduce(stream, gp);
+        launch_contrib_gather(stream, gp);
+    });
+    return GSR_OK;
+}
+
 int gsr_sh_backward_views_chunked(int P, int D, int M, int V, int64_t chunk_len, const float *means3D,
                                   const float *campos, const float *dL_dcolors_sh, float *dL_dsh, void *stream_ptr) {
     if (P < 0 || V < 0) return fail(GSR_ERR_ARG, "P and V must be >= 0");
@@ -1446,6 +1529,28 @@ int gsr_densify_classify(const gsr_densify_args *args, void *workspace, int32_t 
     p.preserve_idx = preserve_idx;
     StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
     launch_densify_classify((hipStream_t)stream_ptr, p);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_densify_classify_keep(int64_t N, const uint8_t *keep_mask, void *workspace, int32_t *counts,
+                              int64_t *preserve_idx, void *stream_ptr) {
+    if (N < 0 || N > 0x7fffffffLL) return fail(GSR_ERR_ARG, "densify: 0 <= N < 2^31");
+    if (!counts) return fail(GSR_ERR_ARG, "densify: null counts");
+    if (N > 0 && (!keep_mask || !workspace || !preserve_idx)) return fail(GSR_ERR_ARG, "densify: null input");
+    size_t o_rank, o_blk, o_cls;
+    densify_ws(N, &o_rank, &o_blk, &o_cls);
+    char *ws = (char *)workspace;
+    DensifyParams p{};
+    p.N = N;
+    p.dst_map = (int32_t *)ws;
+    p.split_rank = (int32_t *)(ws + o_rank);
+    p.block_counts = (int32_t *)(ws + o_blk);
+    p.row_class = (uint8_t *)(ws + o_cls);
+    p.counts = counts;
+    p.preserve_idx = preserve_idx;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_densify_classify_keep((hipStream_t)stream_ptr, p, keep_mask);
     GSR_HIP(hipGetLastError());
     return GSR_OK;
 }

@@ -94,6 +94,30 @@ __global__ __launch_bounds__(DN_THREADS) void densify_classify_kernel(DensifyPar
     }
 }
 
+// the classes from a caller's keep mask (gsr_densify_classify_keep): kept or pruned, never cloned or split
+__global__ __launch_bounds__(DN_THREADS) void densify_classify_keep_kernel(DensifyParams p,
+                                                                           const uint8_t *__restrict__ keep_mask) {
+    __shared__ uint64_t s_wave[DN_THREADS / 64];
+    const int64_t r0 = (int64_t)blockIdx.x * DN_ROWS + (int64_t)threadIdx.x * DN_PER;
+    uint32_t k = 0;
+#pragma unroll
+    for (int j = 0; j < DN_PER; j++) {
+        const int64_t i = r0 + j;
+        if (i < p.N) {
+            const uint8_t cl = keep_mask[i] ? DN_KEEP : 0;
+            p.row_class[i] = cl;
+            k += cl;
+        }
+    }
+    uint64_t total;
+    block_exscan_u64<DN_THREADS>(dn_pack(k, 0, 0), s_wave, &total);
+    if (threadIdx.x == 0) {
+        p.block_counts[3 * blockIdx.x] = (int32_t)dn_field(total, 0);
+        p.block_counts[3 * blockIdx.x + 1] = 0;
+        p.block_counts[3 * blockIdx.x + 2] = 0;
+    }
+}
+
 // one workgroup: block_counts -> exclusive block offsets (in place), counts[0..2] = totals
 __global__ __launch_bounds__(DN_SCAN_THREADS) void densify_scan_blocks_kernel(int32_t *block_counts, int nblocks,
                                                                               int32_t *counts) {
@@ -220,6 +244,17 @@ void launch_densify_classify(hipStream_t s, const DensifyParams &p) {
         return;
     }
     densify_classify_kernel<<<(unsigned)nb, DN_THREADS, 0, s>>>(p);
+    densify_scan_blocks_kernel<<<1, DN_SCAN_THREADS, 0, s>>>(p.block_counts, (int)nb, p.counts);
+    densify_map_kernel<<<(unsigned)nb, DN_THREADS, 0, s>>>(p);
+}
+
+void launch_densify_classify_keep(hipStream_t s, const DensifyParams &p, const uint8_t *keep_mask) {
+    const int64_t nb = densify_blocks(p.N);
+    if (nb == 0) {
+        (void)hipMemsetAsync(p.counts, 0, 3 * sizeof(int32_t), s);
+        return;
+    }
+    densify_classify_keep_kernel<<<(unsigned)nb, DN_THREADS, 0, s>>>(p, keep_mask);
     densify_scan_blocks_kernel<<<1, DN_SCAN_THREADS, 0, s>>>(p.block_counts, (int)nb, p.counts);
     densify_map_kernel<<<(unsigned)nb, DN_THREADS, 0, s>>>(p);
 }

@@ -340,6 +340,37 @@ struct FeatGatherParams {
 };
 void launch_feat_gather(hipStream_t s, const FeatGatherParams &p);
 
+// ---- per-Gaussian contribution statistics (gsr_contrib.hip) ----
+// The colour forward replayed once more, forward only: per contributing (Gaussian, pixel) pair the value
+// v = [m(pix) *] alpha_i T_i; per instance the wave's count, sum and max of v go to the instance's 16-B row
+// {count, sum bits, max bits, 0} by expansion index (zeros for a loaded instance no pixel takes).
+struct ContribWalkParams {
+    int W, H, gx, gy, num_tiles;
+    const uint2 *ranges;
+    const uint32_t *point_list, *n_contrib, *tile_last, *tile_loaded, *sorted_u;
+    const GRec *rec;
+    const float *pixel_weights;  // (H,W) or null: a pixel whose weight is not > 0 is left out
+    uint4 *rows;                 // R
+    int strip_exact;             // as RenderFwdParams::strip_exact (set by launch)
+};
+void launch_contrib_walk(hipStream_t s, const ContribWalkParams &p);
+// count / wsum / wmax (P each, any null) from the rows in instance order, by radius and inv only (the live flags belong
+// to the backward composite); Gaussians with more than BIG_GAUSSIAN_TILES instances through bigsum (nbig rows), which
+// the launch fills first.  accumulate: count +=, wsum = wsum + total, wmax = max(wmax, max).
+struct ContribGatherParams {
+    int P;
+    GatherSrc src;  // live, live_valid: null
+    const uint4 *rows;
+    uint4 *bigsum;
+    uint32_t nbig;             // big Gaussians, or an upper bound with nbig_dev the device's count
+    const uint32_t *nbig_dev;  // or null
+    int64_t *count;
+    float *wsum, *wmax;
+    int accumulate;
+};
+void launch_contrib_big_reduce(hipStream_t s, const ContribGatherParams &p);
+void launch_contrib_gather(hipStream_t s, const ContribGatherParams &p);
+
 // ---- multi-view SH gradient (gsr_views.hip) ----
 void launch_sh_backward_views(hipStream_t s, int P, int D, int M, int V, int chunk_len, const float *means3D,
                               const float *campos, const float *dcolors_sh, float *dsh);
@@ -437,6 +468,8 @@ struct DensifyApply {
 };
 int64_t densify_blocks(int64_t N);
 void launch_densify_classify(hipStream_t s, const DensifyParams &p);
+// the same maps from a caller's keep mask (N bytes, non-zero = keep): no clones, no splits
+void launch_densify_classify_keep(hipStream_t s, const DensifyParams &p, const uint8_t *keep_mask);
 void launch_densify_apply(hipStream_t s, const DensifyApply &A, int64_t total_blocks);
 
 // ---- PLY records <-> fields (gsr_ply.hip) ----

@@ -11,6 +11,8 @@ working: `_xyz`, `_features_dc`, `_features_rest`, `_opacity`, `_scaling`, `_rot
 * `save_ply(path)`           -- byte-identical to the reference writer (ply.save_ply);
 * `update_max_radii2D`, `update_xyz_gradient`, `densify_and_prune(..., optimizer=None)` -- densify.py
   (with `optimizer=` the Adam state is re-indexed in the same launch as the parameters);
+* `accumulate_contributions`, `reset_contributions`, `prune_by_contribution` -- densify.py: the
+  per-Gaussian hit count / weight sum / weight max of GaussianRasterizer.contributions over a pass of views;
 * `reset_opacity`, `reset_max_radii2D`, `reset_xyz_gradient`, `step_sh_degree`, `ready_for_*`.
 
 `spatial_scale` is passed directly (the reference derives it from COLMAP cameras with pycolmap,
@@ -133,6 +135,20 @@ class GaussianModel(nn.Module):
         return _densify.densify_and_prune(self, densify_grad_threshold, clone_size_threshold,
                                           prune_opacity_threshold, prune_size_threshold,
                                           prune_screensize_threshold, optimizer=optimizer, generator=generator)
+
+    # ---- contribution statistics and pruning by them (densify.py) ----
+    contrib_count = contrib_wsum = contrib_wmax = None  # created by accumulate_contributions
+
+    def accumulate_contributions(self, stats=None, rasterizer=None, **render_args) -> None:
+        _densify.accumulate_contributions(self, stats, rasterizer=rasterizer, **render_args)
+
+    def reset_contributions(self) -> None:
+        _densify.reset_contributions(self)
+
+    def prune_by_contribution(self, score="wmax", threshold: Optional[float] = None,
+                              keep_ratio: Optional[float] = None, optimizer=None) -> torch.Tensor:
+        return _densify.prune_by_contribution(self, score, threshold=threshold, keep_ratio=keep_ratio,
+                                              optimizer=optimizer)
 
     @torch.no_grad()
     def reset_opacity(self):

@@ -400,6 +400,73 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
         cov3D_precomp=dcov if st.cov3D_precomp is not None else None, cov3D=dcov)
 
 
+def _pixel_weights(pixel_weights, H: int, W: int, device):
+    """The weight image as a contiguous float32 (H,W) tensor on the device (None stays None); RuntimeError otherwise."""
+    if pixel_weights is None:
+        return None
+    if not torch.is_tensor(pixel_weights) or tuple(pixel_weights.shape) not in ((H, W), (1, H, W)):
+        raise RuntimeError(f"pixel_weights must have shape ({H}, {W}) or (1, {H}, {W}), got "
+                           f"{tuple(pixel_weights.shape) if torch.is_tensor(pixel_weights) else type(pixel_weights).__name__}")
+    if pixel_weights.dtype != torch.float32:
+        raise RuntimeError(f"pixel_weights must be float32 (got {pixel_weights.dtype})")
+    if pixel_weights.device != device:
+        pixel_weights = pixel_weights.to(device)
+    return pixel_weights.detach().reshape(H, W).contiguous()
+
+
+_CONTRIB_DTYPES = dict(count=torch.int64, wsum=torch.float32, wmax=torch.float32)
+
+
+def contributions_raw(state: ForwardState, raster_settings, pixel_weights=None, out=None, accumulate=False):
+    """One call of gsr_contributions on a forward's state: per Gaussian, over the (Gaussian, pixel) pairs the colour
+    forward composited, dict(count (P,) int64, wsum (P,) float32, wmax (P,) float32) -- the number of pairs, and the
+    sum and the max of the compositing weight w = alpha T, the colour render's own.  What pruning and budgeting
+    methods reduce over views (LightGaussian: wsum, RadSplat: wmax, Mini-Splatting / Taming-3DGS: count).
+    pixel_weights (H,W) or (1,H,W) float32: the pair's value is m(pix) * w instead (error-based densification), and a
+    pixel whose m is not > 0 is left out of all three.  Exactly 0 for a Gaussian that is culled or that no pixel
+    takes; deterministic (no float atomics); the state is only read, so a backward_raw after it has the bits it has
+    without.  `out` may supply any of the three as contiguous (P,) tensors of those dtypes: then only those are
+    produced (the others are None in the result), so each can be asked for alone.  accumulate=True adds this view to
+    the buffers in `out` (count +=, wsum = wsum + this view's sum, wmax = max) and needs `out`."""
+    rs, st = raster_settings, state
+    device = st.radii.device
+    P = int(st.radii.shape[0])
+    H, W = int(rs.image_height), int(rs.image_width)
+    out = dict(out or {})
+    for name in out:
+        if name not in _CONTRIB_DTYPES:
+            raise RuntimeError(f"out[{name!r}]: the outputs are count, wsum and wmax")
+    if accumulate and not out:
+        raise RuntimeError("accumulate=True needs the buffers to add to in out")
+    res = dict.fromkeys(_CONTRIB_DTYPES)  # with `out`, the entries it does not hold stay None: not produced
+    for name, dtype in _CONTRIB_DTYPES.items():
+        t = out.get(name)
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) != (P,) or t.dtype != dtype or not t.is_contiguous():
+            raise RuntimeError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape ({P},)")
+        if t.device != device:
+            raise RuntimeError(f"out[{name!r}] must be on {device}")
+        res[name] = t
+    m = _pixel_weights(pixel_weights, H, W, device)
+    if device.type != "cuda":
+        raise RuntimeError("the MI355X rasterizer needs its inputs on a HIP device (tensor.device.type == 'cuda')")
+    lib = _native.load()
+    if not out:
+        res = {name: torch.empty(P, dtype=dtype, device=device) for name, dtype in _CONTRIB_DTYPES.items()}
+    bufs = _Buffers(device)
+    a = _native.ContribArgs(P=P, W=W, H=H, R=st.num_rendered, num_big=st.num_big, radii=_ptr(st.radii),
+                            geom_buffer=_ptr(st.geom_buffer), binning_buffer=_ptr(st.binning_buffer),
+                            image_buffer=_ptr(st.image_buffer), pixel_weights=_ptr(m), count=_ptr(res["count"]),
+                            wsum=_ptr(res["wsum"]), wmax=_ptr(res["wmax"]), accumulate=int(bool(accumulate)))
+    if P:
+        with torch.cuda.device(device):
+            rc = _native.call_contributions(lib, a, bufs.callback, _stream_handle(device))
+        bufs.raise_pending()
+        _native.check(rc, "rasterize_contributions")
+    return res
+
+
 def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_out_depth, chunks, on_chunk=None,
                      compact_sh=False, accumulate_stats=False, after_composite=None, grad_out_alpha=None,
                      bg_out=None, abs_stats=False):
@@ -603,6 +670,23 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                      *camera)
 
 
+@torch.no_grad()
+def rasterize_contributions(means3D, opacities, raster_settings, shs=None, colors_precomp=None, scales=None,
+                            rotations=None, cov3D_precomp=None, pixel_weights=None, out=None, accumulate=False):
+    """One forward_raw, then contributions_raw on its state: (dict(count, wsum, wmax), radii).  Colours do not enter
+    the weights: with neither shs nor colors_precomp the forward renders a zero (P,3) colors_precomp."""
+    if shs is not None and colors_precomp is not None:
+        raise Exception("Please provide at most one of either SHs or precomputed colors!")
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or (
+            (scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+    if shs is None and colors_precomp is None:
+        colors_precomp = torch.zeros(means3D.shape[0], 3, dtype=torch.float32, device=means3D.device)
+    res = forward_raw(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings)
+    radii, state = res[1], res[-1]
+    return contributions_raw(state, raster_settings, pixel_weights=pixel_weights, out=out, accumulate=accumulate), radii
+
+
 def sh_backward_views(means3D: torch.Tensor, campos: torch.Tensor, dcolors_sh: torch.Tensor, sh_degree: int, M: int,
                       out: Optional[torch.Tensor] = None, chunk_len: int = 0) -> torch.Tensor:
     """dL/dshs (P,M,3) summed over V views from the compact per-view factors: campos (V,3) and the clamp-masked
@@ -675,3 +759,12 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs, return_alpha=self.return_alpha, absgrad=self.absgrad,
                                    features=features)
+
+    def contributions(self, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                      cov3D_precomp=None, pixel_weights=None, out=None, accumulate=False):
+        """(dict(count, wsum, wmax), radii) of this view: the per-Gaussian hit count and the sum and max of the
+        compositing weight, without a gradient (rasterize_contributions, contributions_raw)."""
+        return rasterize_contributions(means3D, opacities, self.raster_settings, shs=shs,
+                                       colors_precomp=colors_precomp, scales=scales, rotations=rotations,
+                                       cov3D_precomp=cov3D_precomp, pixel_weights=pixel_weights, out=out,
+                                       accumulate=accumulate)

@@ -43,7 +43,8 @@ enum {
     GSR_BUF_IMAGE = 2,
     GSR_BUF_BWD_SCRATCH = 3,
     GSR_BUF_CAMERA_PARTIALS = 4, /* gsr_backward, only when a camera gradient is asked for; free after the call */
-    GSR_BUF_BACKGROUND_PARTIALS = 5 /* gsr_backward_ext, only when dL_dbackground is asked for; free after the call */
+    GSR_BUF_BACKGROUND_PARTIALS = 5, /* gsr_backward_ext, only when dL_dbackground is asked for; free after the call */
+    GSR_BUF_CONTRIB_SCRATCH = 6 /* gsr_contributions (gsr_contrib_scratch_bytes); free after the call */
 };
 
 enum {
@@ -267,6 +268,40 @@ int gsr_forward_features(gsr_forward_args *args, const gsr_composite_ext *ext, c
 int gsr_backward_features(const gsr_backward_args *args, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
                           const gsr_features_ext *feat, gsr_alloc_fn alloc, void *alloc_ctx, void *stream);
 
+/* Per-Gaussian contribution statistics of one forward, for pruning and budgeting (LightGaussian's significance: the
+ * sum; RadSplat: the max; Mini-Splatting / Taming-3DGS: the hit count; error-based densification: the sum under a
+ * per-pixel error image).  Forward only: no gradient is involved.  GSR_ABI_VERSION and every other struct stay as they
+ * are; this one is versioned by its own size like the ext structs.
+ *   A pair (Gaussian i, pixel pix) CONTRIBUTES when the colour forward composited it: the pair test is the feature
+ *   replay's (sorted index below the pixel's contributor count, the composite's alpha decision; under the "guard" knob
+ *   the guarded one).  Its value is v = w_i(pix) = alpha_i T_i, the colour render's own weight, or with pixel_weights
+ *   v = m(pix) * w_i(pix) as one fp32 product; a pixel whose m is not > 0 (zero, negative, NaN) is left out of
+ *   everything.  Per Gaussian, over its contributing pairs with a pixel that is not left out:
+ *     count[i] (int64) their number, wsum[i] the sum of v, wmax[i] the max of v (0 where there are none).
+ *   All three are exactly 0 for a Gaussian that is culled or that no pixel takes; every element is written.
+ *   accumulate != 0: count += , wsum = wsum + this view's sum (one fp32 add), wmax = max(wmax, this view's max), so a
+ *   pass over views keeps one set of buffers.
+ * The sums are formed in a fixed order (per instance inside its wave, then per Gaussian in instance order; no float
+ * atomics): two calls give the same bits.  The call only reads the forward's three buffers: a gsr_backward on the same
+ * state afterwards gives the bits it gives without it.  Scratch: one GSR_BUF_CONTRIB_SCRATCH buffer of
+ * gsr_contrib_scratch_bytes(R, num_big) bytes through the callback (16 B per instance and per big Gaussian).
+ * GSR_ERR_ARG, before any device work or allocation: every output NULL, a forward buffer (or radii) missing while
+ * R > 0, struct_size ending before the first pointer field.  With P == 0 nothing is written; with R == 0 (everything
+ * culled) the outputs are zeros, or under accumulate left as they are.  Launches go on `stream`, on its device. */
+typedef struct gsr_contrib_args {
+    size_t struct_size;            /* sizeof as the caller was built; fields past it are read as NULL / 0 */
+    int P, W, H;
+    int64_t R, num_big;            /* num_rendered and num_big_out of the forward (num_big < 0: read on the device) */
+    const int32_t *radii;          /* (P) from the forward */
+    const void *geom_buffer, *binning_buffer, *image_buffer; /* from the forward; only read */
+    const float *pixel_weights;    /* (H,W) or NULL */
+    int64_t *count;                /* (P) or NULL (not produced) */
+    float *wsum, *wmax;            /* (P) each, or NULL */
+    int accumulate;
+} gsr_contrib_args;
+size_t gsr_contrib_scratch_bytes(int64_t R, int64_t num_big);
+int gsr_contributions(const gsr_contrib_args *args, gsr_alloc_fn alloc, void *alloc_ctx, void *stream);
+
 /* Multi-view SH gradient from compact per-view factors (no counterpart in the reference, whose batch size is
  * one view: gs_lightning_module.py:139-141).  dL_dsh[g] = sum_v basis(normalize(means3D[g] - campos[v]))
  * (x) dL_dcolors_sh[v][g], i.e. the sum over views of gsr_backward's dL_dsh -- what an all-reduce of dL_dsh
@@ -386,6 +421,12 @@ size_t gsr_densify_workspace_bytes(int64_t N);
 /* preserve_idx (N int64): the first counts[0] entries are the kept row indices (the reference's return value). */
 int gsr_densify_classify(const gsr_densify_args *args, void *workspace, int32_t *counts, int64_t *preserve_idx,
                          void *stream);
+
+/* The same row maps from a caller's keep mask (N bytes on the device, non-zero = keep) -- pruning by any criterion,
+ * e.g. the contribution statistics above: no clones, no splits (counts[1] = counts[2] = 0).  The workspace is then
+ * scattered through gsr_densify_apply like gsr_densify_classify's (z may be NULL). */
+int gsr_densify_classify_keep(int64_t N, const uint8_t *keep_mask, void *workspace, int32_t *counts,
+                              int64_t *preserve_idx, void *stream);
 
 enum { GSR_FIELD_PLAIN = 0, GSR_FIELD_XYZ = 1, GSR_FIELD_SCALING = 2, GSR_FIELD_STAT = 3 };
 typedef struct gsr_densify_field {
