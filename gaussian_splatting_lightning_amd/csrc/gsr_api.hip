@@ -529,61 +529,166 @@ void gsr_state_layout_query(int P, int64_t R, int W, int H, gsr_state_layout *ca
     memcpy(caller, &full, want);
 }
 
-int gsr_forward(gsr_forward_args *a, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr,
-                int64_t *num_rendered) {
-    return gsr_forward_ext(a, nullptr, alloc, alloc_ctx, stream_ptr, num_rendered);
+// The state a forward call builds in its three buffers, as the forward fills it and as the backward and
+// gsr_contributions recover it from the caller's buffers (recover_state)
+struct RasterState {
+    int W, H, gx, gy;
+    uint32_t T, R;
+    // recover_state with num_big < 0: not known on the host (the upstream backward signature has no such argument,
+    // gsr_torch_ext): nbig is then the most there can be (each has > BIG_GAUSSIAN_TILES instances), which sizes the
+    // sums, and nbig_dev the count the preprocess left in the geometry buffer, which the reductions read; else nbig is
+    // exact, nbig_dev null
+    uint32_t nbig;
+    const uint32_t *nbig_dev;
+    GeomState g;
+    BinningState b;
+    ImageState im;
+};
+static void set_image(RasterState &s, int W, int H) {
+    s.W = W, s.H = H;
+    s.gx = (W + BLOCK_X - 1) / BLOCK_X, s.gy = (H + BLOCK_Y - 1) / BLOCK_Y;
+    s.T = (uint32_t)(s.gx * s.gy);
+}
+static void recover_state(RasterState &s, int P, int W, int H, int64_t R, int64_t num_big, const void *geom,
+                          const void *binning, const void *image) {
+    set_image(s, W, H);
+    s.R = (uint32_t)R;
+    carve_geom(static_cast<char *>(const_cast<void *>(geom)), P, s.g);
+    carve_binning(static_cast<char *>(const_cast<void *>(binning)), s.R, s.T, s.b);
+    carve_image(static_cast<char *>(const_cast<void *>(image)), W, H, s.im);
+    s.nbig = num_big < 0 ? s.R / (BIG_GAUSSIAN_TILES + 1) + 1 : (uint32_t)num_big;
+    s.nbig_dev = num_big < 0 ? s.g.counters + CNT_BIG : nullptr;
+}
+// What the gathers test (gsr_gather.h).  live: the backward composite's flags apply ("bwd_live" 1); the validity word
+// goes with every backward, as it always did, and is null only where no backward composite ran (gsr_contributions)
+static GatherSrc gather_src(const int *radii, const RasterState &s, bool backward, bool live) {
+    GatherSrc src;
+    src.radii = radii; src.tiles = s.g.tiles; src.inst_start = s.g.inst_start;
+    src.big_slot = s.g.big_slot; src.big_list = s.g.big_list; src.inv = s.b.inv;
+    src.live = backward && live ? s.g.live : nullptr;
+    src.live_valid = backward ? s.g.counters + CNT_LIVE_VALID : nullptr;
+    return src;
+}
+// What the replays read (gsr_replay.h)
+static ReplaySrc replay_src(const RasterState &s) {
+    ReplaySrc r;
+    r.W = s.W; r.H = s.H; r.gx = s.gx; r.gy = s.gy; r.num_tiles = (int)s.T;
+    r.ranges = s.im.ranges; r.point_list = s.b.point_list; r.n_contrib = s.im.n_contrib;
+    r.tile_last = s.im.tile_last; r.tile_loaded = s.im.tile_loaded; r.sorted_u = s.b.sorted_u;
+    r.rec = s.g.rec;
+    return r;
 }
 
-int gsr_forward_ext(gsr_forward_args *a, const gsr_composite_ext *ext, gsr_alloc_fn alloc, void *alloc_ctx,
-                    void *stream_ptr, int64_t *num_rendered) {
-    return gsr_forward_features(a, ext, nullptr, alloc, alloc_ctx, stream_ptr, num_rendered);
-}
-
-int gsr_forward_features(gsr_forward_args *a, const gsr_composite_ext *ext, const gsr_features_ext *feat,
-                         gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr, int64_t *num_rendered) {
-    if (!a || !alloc || !num_rendered) return fail(GSR_ERR_ARG, "null argument");
+// One forward call's state: what the argument checks read, the state it builds, and what one stage leaves for the
+// next.  Each stage below takes it whole, in the driver's order (gsr_forward_features).
+struct FwdCall : RasterState {
+    gsr_forward_args *a;
+    gsr_alloc_fn alloc;
+    void *alloc_ctx;
+    hipStream_t stream;
+    bool dbg;
+    int dev;  // the stream's device (StreamDeviceGuard)
     CompositeExt e;
-    int rc = read_composite_ext(ext, a->background, e);
-    if (rc) return rc;
     FeaturesExt fx;
-    rc = read_features_ext(feat, a->P, fx);
+    int P;
+    // the readback: this thread's pinned words and event, the sequence number awaited, and whether the preprocess
+    // publishes into the words ("rb_spin") or a copy plus the event brings the counters
+    uint32_t *hw;
+    hipEvent_t rb_ev;
+    uint32_t seq;
+    bool rb_spin;
+    InflightReadback *inflight;  // the driver's
+    int bk, lpt;                 // the "bucket" and "lpt" knobs
+    bool bk_possible;            // the tile count admits the bucket path: its count pass is queued
+    BucketParams bp;
+    char *bin;                   // the binning buffer requested before the wait (bin_cap instances), or null
+    int64_t bin_cap;
+    uint32_t kmin, kmax;         // the kept depth keys' range (kmin > kmax: none kept)
+    bool bucket;                 // bucket binning, else the radix path
+    bool xcd_fwd;                // the composite runs the per-XCD LPT orders (set by the bucket scatter)
+};
+
+// The side structs and every argument check, in the order callers see their errors
+static int fwd_check_args(FwdCall &c, const gsr_composite_ext *ext, const gsr_features_ext *feat) {
+    gsr_forward_args *a = c.a;
+    int rc = read_composite_ext(ext, a->background, c.e);
     if (rc) return rc;
-    if (fx.given && !fx.out_features) return fail(GSR_ERR_ARG, "gsr_features_ext: out_features is required");
+    rc = read_features_ext(feat, a->P, c.fx);
+    if (rc) return rc;
+    if (c.fx.given && !c.fx.out_features) return fail(GSR_ERR_ARG, "gsr_features_ext: out_features is required");
     rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
                       a->scales, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
-                      e.background_image ? e.background_image : a->background);
+                      c.e.background_image ? c.e.background_image : a->background);
     if (rc) return rc;
     if (!a->out_color || (a->P > 0 && !a->radii)) return fail(GSR_ERR_ARG, "out_color and radii are required");
-    hipStream_t stream = (hipStream_t)stream_ptr;
-    StreamDeviceGuard device_guard(stream);
-    const bool dbg = a->debug != 0;
-    const int P = a->P, W = a->W, H = a->H;
-    const int gx = (W + BLOCK_X - 1) / BLOCK_X, gy = (H + BLOCK_Y - 1) / BLOCK_Y;
-    const uint32_t T = (uint32_t)(gx * gy);
-    *num_rendered = 0;
-    a->num_big_out = 0;
-    if (P == 0) {
-        // the reference returns its zero-initialised outputs untouched when P == 0; with a gsr_composite_ext the
-        // colour is what the composite writes where no Gaussian reaches: the background, alpha 0
-        if (e.given) {
-            launch_background_fill(stream, (size_t)W * H, a->background, e.background_image, a->out_color, e.out_alpha);
-            GSR_HIP(hipGetLastError());
-        } else {
-            GSR_HIP(hipMemsetAsync(a->out_color, 0, sizeof(float) * 3 * (size_t)W * H, stream));
-        }
-        if (a->out_invdepth) GSR_HIP(hipMemsetAsync(a->out_invdepth, 0, sizeof(float) * (size_t)W * H, stream));
-        if (fx.given) GSR_HIP(hipMemsetAsync(fx.out_features, 0, sizeof(float) * fx.C * (size_t)W * H, stream));
-        return GSR_OK;
-    }
+    c.P = a->P;
+    set_image(c, a->W, a->H);
+    return GSR_OK;
+}
 
-    GeomState g;
-    char *geom = alloc(alloc_ctx, GSR_BUF_GEOM, carve_geom(nullptr, P, g));
+// P == 0: the reference returns its zero-initialised outputs untouched; with a gsr_composite_ext the colour is what
+// the composite writes where no Gaussian reaches: the background, alpha 0
+static int fwd_empty_scene(FwdCall &c) {
+    gsr_forward_args *a = c.a;
+    hipStream_t stream = c.stream;
+    const size_t HW = (size_t)c.W * c.H;
+    if (c.e.given) {
+        launch_background_fill(stream, HW, a->background, c.e.background_image, a->out_color, c.e.out_alpha);
+        GSR_HIP(hipGetLastError());
+    } else {
+        GSR_HIP(hipMemsetAsync(a->out_color, 0, sizeof(float) * 3 * HW, stream));
+    }
+    if (a->out_invdepth) GSR_HIP(hipMemsetAsync(a->out_invdepth, 0, sizeof(float) * HW, stream));
+    if (c.fx.given) GSR_HIP(hipMemsetAsync(c.fx.out_features, 0, sizeof(float) * c.fx.C * HW, stream));
+    return GSR_OK;
+}
+
+// The bucket path's parameters as far as they are known before the instance total (its count pass), the walk block
+// count included
+static int fwd_bucket_plan(FwdCall &c) {
+    const GeomState &g = c.g;
+    const ImageState &im = c.im;
+    const int P = c.P;
+    BucketParams &bp = c.bp;
+    bp.P = (uint32_t)P; bp.T = c.T; bp.gx = c.gx; bp.nbig = g.counters + CNT_BIG;
+    bp.nb = std::max(1u, std::min({(uint32_t)tuning("bk_blocks", 256), BK_MAX_BLOCKS, div_up(P, 1024)}));
+    bp.gper = div_up(div_up(P, bp.nb), 256) * 256;  // whole preprocess blocks
+    bp.nr = div_up(P, bp.gper);
+    // extra walk blocks for the big rects (used only when the device's big-Gaussian count exceeds nr: bk_walk_blocks);
+    // the block count is fixed here, before that count is read back.  2000 sparse-scene Gaussians at 1080p ran their
+    // big rects on 2 blocks (count + scatter walks 220 + 310 us).  Only below half of that count of
+    // range blocks: at cfg 3 (245 range blocks) 11 extra blocks measured +10 us of scatter (profiles/r4s_*)
+    const uint32_t big_blocks = std::min((uint32_t)tuning("bk_big_blocks", 256), BK_MAX_BLOCKS);
+    bp.nb = 2 * bp.nr < big_blocks ? big_blocks : bp.nr;
+    bp.tiles = g.tiles; bp.inst_start = g.inst_start; bp.block_sums = g.block_sums; bp.depth_key = g.depth_key;
+    bp.big_list = g.big_list; bp.exp_rec = g.exp_rec;
+    bp.hist = im.bk_hist; bp.hist_pre = im.bk_hist_pre; bp.tile_next = im.bk_tile_next; bp.reg_start = im.bk_reg_start;
+    bp.tile_start = im.bk_tile_start; bp.ranges = im.ranges;
+    bp.tile_last = im.tile_last; bp.tile_loaded = im.tile_loaded;
+    bp.lpt_bcnt = im.lpt_bcnt;
+    bp.ticket = g.counters + CNT_COL_TICKET; bp.tile_status = g.tile_status; bp.err = g.counters + CNT_OVERFLOW;
+    bp.long_list = im.bk_long_list; bp.long_cnt = g.counters + CNT_LONG;
+    bp.lb_patience = (uint32_t)tuning("lb_patience", 1 << 16); bp.lb_force = tuning("lb_force", 0);
+    bp.xcd_major = tuning("bk_xcd", 1);
+    // every buffer the column pass clears must be wired (a null one would fault the GPU, not fail here)
+    if (!bp.tile_last || !bp.tile_loaded || !bp.ranges || !bp.tile_start || !bp.hist_pre)
+        return fail(GSR_ERR_ARG, "internal: bucket binning buffer not set");
+    return GSR_OK;
+}
+
+// The geometry and image buffers, the counter clear, the preprocess and -- queued right behind it, before the host
+// waits for the total -- the bucket path's count pass
+static int fwd_preprocess(FwdCall &c) {
+    gsr_forward_args *a = c.a;
+    hipStream_t stream = c.stream;
+    const int P = c.P, W = c.W, H = c.H;
+    GeomState &g = c.g;
+    char *geom = c.alloc(c.alloc_ctx, GSR_BUF_GEOM, carve_geom(nullptr, P, g));
     if (!geom) return fail(GSR_ERR_ALLOC, "geometry buffer allocation failed");
     carve_geom(geom, P, g);
-    ImageState im;
-    char *img = alloc(alloc_ctx, GSR_BUF_IMAGE, carve_image(nullptr, W, H, im));
+    char *img = c.alloc(c.alloc_ctx, GSR_BUF_IMAGE, carve_image(nullptr, W, H, c.im));
     if (!img) return fail(GSR_ERR_ALLOC, "image buffer allocation failed");
-    carve_image(img, W, H, im);
+    carve_image(img, W, H, c.im);
     // counters + instance-scan and tile-scan look-back words; rounded up to the carver's 256-B alignment (the
     // next array starts there) so the memset is one aligned fill kernel, not an aligned fill plus a tail
     const size_t clear_bytes = align_up((size_t)(reinterpret_cast<char *>(g.tile_status + BK_MAX_TILES / 32 + 1) -
@@ -591,7 +696,7 @@ int gsr_forward_features(gsr_forward_args *a, const gsr_composite_ext *ext, cons
     launch_zero16(stream, g.counters, clear_bytes);  // a plain kernel: the runtime's fill measured slower
 
     PreprocessParams pp;
-    pp.P = P; pp.D = a->D; pp.M = a->M; pp.W = W; pp.H = H; pp.gx = gx; pp.gy = gy;
+    pp.P = P; pp.D = a->D; pp.M = a->M; pp.W = W; pp.H = H; pp.gx = c.gx; pp.gy = c.gy;
     pp.tan_fovx = a->tan_fovx; pp.tan_fovy = a->tan_fovy;
     pp.focal_x = W / (2.0f * a->tan_fovx);
     pp.focal_y = H / (2.0f * a->tan_fovy);
@@ -608,233 +713,241 @@ int gsr_forward_features(gsr_forward_args *a, const gsr_composite_ext *ext, cons
     // The instance total only needs the per-Gaussian tile counts, so it is read back right after the
     // preprocess: its last workgroup writes the counters into pinned host memory and then a sequence word the
     // host polls ("rb_spin" 1, default; 0: a copy plus an event, one more kernel and a barrier on the stream).
-    // The bucket path's count pass needs no total either: whenever the tile count admits that path it is queued
-    // right behind the preprocess, so the GPU runs it while the host waits (its scratch is in the image buffer;
-    // if the total then selects the radix path, its results are simply unused).
-    uint32_t *hw = pinned_words(device_guard.dev);
-    hipEvent_t rb_ev = readback_event(device_guard.dev);
-    if (!hw || !rb_ev) return fail(GSR_ERR_HIP, "pinned host buffer / event allocation failed");
-    const bool rb_spin = tuning("rb_spin", 1) != 0 && !dbg;
-    const uint32_t seq = next_readback_seq(device_guard.dev);
-    pp.host_words = rb_spin ? hw : nullptr;
+    c.hw = pinned_words(c.dev);
+    c.rb_ev = readback_event(c.dev);
+    if (!c.hw || !c.rb_ev) return fail(GSR_ERR_HIP, "pinned host buffer / event allocation failed");
+    c.rb_spin = tuning("rb_spin", 1) != 0 && !c.dbg;
+    c.seq = next_readback_seq(c.dev);
+    pp.host_words = c.rb_spin ? c.hw : nullptr;
     pp.stamps = tuning("stamp", 0) ? stamp_buffer(3) : nullptr;
-    pp.seq = seq;
-    InflightReadback inflight;  // armed before the launch: an error reported after it still waits for the kernel
-    inflight.s = stream;
-    inflight.armed = rb_spin;
+    pp.seq = c.seq;
+    // armed before the launch: an error reported after it, by this stage or a later one, still waits for the kernel
+    // (the driver's frame holds it until the call returns)
+    c.inflight->s = stream;
+    c.inflight->armed = c.rb_spin;
     // the kept depth keys' range, for the radix path's relative depth sort: only where that sort can run (multi-kernel
     // depth sorts, P above the onesweep limit); else the range words stay empty and the sort takes its 32-bit keys
     const uint32_t os_max = (uint32_t)tuning("onesweep_max_n", 3 << 20);
     pp.depth_range = (tuning("depth_rel", 1) && (uint32_t)P > os_max) ? 1 : 0;
-    GSR_STAGE(ST_PREPROCESS, dbg, launch_preprocess(stream, pp));
-    if (!rb_spin) {
-        GSR_HIP(hipMemcpyAsync(hw, g.counters, CNT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        GSR_HIP(hipEventRecord(rb_ev, stream));
+    GSR_STAGE(ST_PREPROCESS, c.dbg, launch_preprocess(stream, pp));
+    if (!c.rb_spin) {
+        GSR_HIP(hipMemcpyAsync(c.hw, g.counters, CNT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        GSR_HIP(hipEventRecord(c.rb_ev, stream));
     }
-    const int bk = tuning("bucket", 1);
-    const bool bk_possible = bk == 2 ? T <= BK_MAX_TILES : bk == 1 && T <= BK_MAX_TILES / 2;
-    const int lpt = tuning("lpt", 1);
-    BucketParams bp = {};
-    if (bk_possible) {
-        bp.P = (uint32_t)P; bp.T = T; bp.gx = gx; bp.nbig = g.counters + CNT_BIG;
-        bp.nb = std::max(1u, std::min({(uint32_t)tuning("bk_blocks", 256), BK_MAX_BLOCKS, div_up(P, 1024)}));
-        bp.gper = div_up(div_up(P, bp.nb), 256) * 256;  // whole preprocess blocks
-        bp.nr = div_up(P, bp.gper);
-        // extra walk blocks for the big rects (used only when the device's big-Gaussian count exceeds nr: bk_walk_blocks);
-        // the block count is fixed here, before that count is read back.  2000 sparse-scene Gaussians at 1080p ran their
-        // big rects on 2 blocks (count + scatter walks 220 + 310 us).  Only below half of that count of
-        // range blocks: at cfg 3 (245 range blocks) 11 extra blocks measured +10 us of scatter (profiles/r4s_*)
-        const uint32_t big_blocks = std::min((uint32_t)tuning("bk_big_blocks", 256), BK_MAX_BLOCKS);
-        bp.nb = 2 * bp.nr < big_blocks ? big_blocks : bp.nr;
-        bp.tiles = g.tiles; bp.inst_start = g.inst_start; bp.block_sums = g.block_sums; bp.depth_key = g.depth_key;
-        bp.big_list = g.big_list; bp.exp_rec = g.exp_rec;
-        bp.hist = im.bk_hist; bp.hist_pre = im.bk_hist_pre; bp.tile_next = im.bk_tile_next; bp.reg_start = im.bk_reg_start; bp.tile_start = im.bk_tile_start; bp.ranges = im.ranges;
-        bp.tile_last = im.tile_last; bp.tile_loaded = im.tile_loaded;
-        bp.lpt_bcnt = im.lpt_bcnt;
-        bp.ticket = g.counters + CNT_COL_TICKET; bp.tile_status = g.tile_status; bp.err = g.counters + CNT_OVERFLOW;
-        bp.long_list = im.bk_long_list; bp.long_cnt = g.counters + CNT_LONG;
-        bp.lb_patience = (uint32_t)tuning("lb_patience", 1 << 16); bp.lb_force = tuning("lb_force", 0);
-        bp.xcd_major = tuning("bk_xcd", 1);
-        // every buffer the column pass clears must be wired (a null one would fault the GPU, not fail here)
-        if (!bp.tile_last || !bp.tile_loaded || !bp.ranges || !bp.tile_start || !bp.hist_pre)
-            return fail(GSR_ERR_ARG, "internal: bucket binning buffer not set");
-        GSR_STAGE(ST_BK_COUNT, dbg, launch_bucket_count(stream, bp));
+    // The bucket path's count pass needs no total either: whenever the tile count admits that path it is queued
+    // right behind the preprocess, so the GPU runs it while the host waits (its scratch is in the image buffer;
+    // if the total then selects the radix path, its results are simply unused).
+    c.bk = tuning("bucket", 1);
+    c.bk_possible = c.bk == 2 ? c.T <= BK_MAX_TILES : c.bk == 1 && c.T <= BK_MAX_TILES / 2;
+    c.lpt = tuning("lpt", 1);
+    if (c.bk_possible) {
+        const int rc = fwd_bucket_plan(c);
+        if (rc) return rc;
+        GSR_STAGE(ST_BK_COUNT, c.dbg, launch_bucket_count(stream, c.bp));
     }
+    return GSR_OK;
+}
+
+// The instance total and the big-Gaussian count, read back; which binning path the total selects
+static int fwd_readback(FwdCall &c) {
+    hipStream_t stream = c.stream;
     // The binning buffer's size depends on the instance total.  Requesting it through the caller's allocator
     // (a Python callback from rasterizer.py) after the readback put ~40 us of host work between the preprocess and
     // the next launch, longer than the queued count passes cover; so with a total from an earlier call on this
-    // thread and device the buffer is requested before the wait, 25 % larger, and only re-requested when the
-    // total exceeds it ("bin_prealloc" 0: always after the wait).
-    BinningState b;
-    char *bin = nullptr;
-    int64_t bin_cap = -1;
-    int64_t &r_hint = readback_hint(device_guard.dev);
+    // thread and device (readback_hint, read here before the wait) the buffer is requested before the wait, 25 %
+    // larger, and only re-requested when the total exceeds it ("bin_prealloc" 0: always after the wait).
+    c.bin = nullptr;
+    c.bin_cap = -1;
+    const int64_t r_hint = readback_hint(c.dev);
     if (r_hint > 0 && tuning("bin_prealloc", 1)) {
-        bin_cap = std::min<int64_t>(r_hint + r_hint / 4 + 4096, 0xffffffffLL);
-        bin = alloc(alloc_ctx, GSR_BUF_BINNING, carve_binning(nullptr, bin_cap, T, b));
-        if (!bin) return fail(GSR_ERR_ALLOC, "binning buffer allocation failed");
+        c.bin_cap = std::min<int64_t>(r_hint + r_hint / 4 + 4096, 0xffffffffLL);
+        c.bin = c.alloc(c.alloc_ctx, GSR_BUF_BINNING, carve_binning(nullptr, c.bin_cap, c.T, c.b));
+        if (!c.bin) return fail(GSR_ERR_ALLOC, "binning buffer allocation failed");
     }
     uint64_t total64 = 0;
-    uint32_t nbig = 0, kmin = 0xffffffffu, kmax = 0;  // the kept depth keys' range (kmin > kmax: none kept)
-    if (rb_spin) {
-        GSR_STAGE(ST_READBACK, dbg, {
-            const int rc = wait_readback(hw, seq, stream, &total64, &nbig, &kmin, &kmax);
+    c.nbig = 0, c.kmin = 0xffffffffu, c.kmax = 0;
+    if (c.rb_spin) {
+        GSR_STAGE(ST_READBACK, c.dbg, {
+            const int rc = wait_readback(c.hw, c.seq, stream, &total64, &c.nbig, &c.kmin, &c.kmax);
             if (rc) return rc;
         });
-        inflight.armed = false;
+        c.inflight->armed = false;  // published: the pinned words are this call's no longer
     } else {
-        GSR_STAGE(ST_READBACK, dbg, GSR_HIP(hipEventSynchronize(rb_ev)));
+        GSR_STAGE(ST_READBACK, c.dbg, GSR_HIP(hipEventSynchronize(c.rb_ev)));
         uint32_t cmax = 0;
         for (int k = 0; k < CNT_NPART; k++) {
             uint64_t part;
-            memcpy(&part, hw + CNT_PARTIALS + 2 * k, sizeof(part));
+            memcpy(&part, c.hw + CNT_PARTIALS + 2 * k, sizeof(part));
             total64 += part;
-            cmax = std::max(cmax, hw[CNT_DMIN + k]);
-            kmax = std::max(kmax, hw[CNT_DMAX + k]);
+            cmax = std::max(cmax, c.hw[CNT_DMIN + k]);
+            c.kmax = std::max(c.kmax, c.hw[CNT_DMAX + k]);
         }
-        kmin = ~cmax;
-        nbig = hw[CNT_BIG];
+        c.kmin = ~cmax;
+        c.nbig = c.hw[CNT_BIG];
     }
     if (total64 > 0xffffffffull) return fail(GSR_ERR_OVERFLOW, "more than 2^32-1 tile instances");
-    const uint32_t R = (uint32_t)total64;
-    *num_rendered = R;
-    a->num_big_out = nbig;
+    c.R = (uint32_t)total64;
     // Bucket binning (gsr_bin.hip) while the tile counters fit a workgroup's LDS with room for two per CU and
     // the tiles are short (per-tile sorts cost n log^2 n): at 1M Gaussians / 1080p (517 instances per tile) it
     // takes 0.20 ms against the radix path's 0.30; at 5M / 4K stress (1240 per tile) 4.4 ms against 1.4.
     // Otherwise the radix path: depth sort, depth-ordered expansion, stable tile sort.
-    const bool bucket = bk_possible && (bk == 2 || (uint64_t)R <= (uint64_t)BK_MAX_MEAN * T);
-    bool xcd_fwd = false;  // the forward composite runs the per-XCD LPT orders (set by the bucket scatter below)
-    bool sorted_exp = false;
-    bool depth_onesweep = false, tile_onesweep = false;  // which sorts ran on the onesweep path (diagnostics)
-    if (bucket) gsr_set_tuning("stat_depth_passes", 0);
-    if (!bucket) {
-        // the depth sort's last pass also writes the tile counts in depth order, so the instance scan reads them
-        // coalesced instead of gathering them through the order (the 16-B expansion records too measured slower: cfg 5
-        // depth sort 0.232 -> 0.352 ms for expand 0.241 -> 0.221 ms, profiles/r6t_libab_sort_gather_cfg5.txt; the
-        // expansion gathers them by rank)
-        constexpr int sg = 1;
-        SortGather ga;
-        ga.src = g.tiles; ga.dst = g.tiles_sorted;
-        bool sorted_recs = false;
-        // Relative depth keys ("depth_rel" 1) where the sort takes the multi-kernel path: the kept keys span
-        // kmax - kmin, so rs_rel_key maps them onto [0, span] and the culled ones onto span + 1, and the sort runs
-        // ceil(bits / 9) passes instead of 4 (cfg 5: 26 bits, 3 passes of 9 bits)
-        int rel_bits = 32;
-        if (tuning("depth_rel", 1) && kmin <= kmax && (uint32_t)P > os_max && kmax - kmin < 0xfffffffeu) {
-            const uint32_t cap = kmax - kmin + 1;
-            rel_bits = 32 - __builtin_clz(cap);
-        }
-        gsr_set_tuning("stat_depth_passes", rel_bits <= 27 ? (rel_bits + 8) / 9 : 4);
-        if (rel_bits <= 27) {
-            GSR_STAGE(ST_DEPTH_SORT, dbg,
-                      launch_depth_sort_rel(stream, g.sort, (uint32_t)P, g.depth_key, kmin, kmax - kmin + 1, rel_bits,
-                                            sg ? &ga : nullptr));
-            sorted_recs = sg != 0;
-        } else {
-            GSR_STAGE(ST_DEPTH_SORT, dbg,
-                      sorted_recs = launch_radix_sort(stream, g.sort, (uint32_t)P, 32, false, g.depth_key,
-                                                      sg ? &ga : nullptr, &depth_onesweep));
-        }
-        const bool sorted_tiles = sorted_recs && (sg & 1);
-        sorted_exp = sorted_recs && (sg & 2);
-        GSR_STAGE(ST_SCAN, dbg,
-                  launch_exclusive_scan_lookback(stream, sorted_tiles ? g.tiles_sorted : g.tiles,
-                                                 sorted_tiles ? nullptr : g.order, (uint32_t)P, g.inst_off,
-                                                 g.scan_status, g.counters + CNT_SCAN_TICKET,
-                                                 g.counters + CNT_OVERFLOW));
-    }
+    c.bucket = c.bk_possible && (c.bk == 2 || (uint64_t)c.R <= (uint64_t)BK_MAX_MEAN * c.T);
+    if (c.bucket) gsr_set_tuning("stat_depth_passes", 0);
+    return GSR_OK;
+}
 
-    r_hint = R;
-    if (!bin || (int64_t)R > bin_cap) {
-        bin = alloc(alloc_ctx, GSR_BUF_BINNING, carve_binning(nullptr, R, T, b));
-        if (!bin) return fail(GSR_ERR_ALLOC, "binning buffer allocation failed");
+// Radix path: the depth sort and the instance scan, launched before the binning buffer is sized so that the GPU
+// runs them meanwhile
+static int fwd_depth_sort(FwdCall &c) {
+    hipStream_t stream = c.stream;
+    GeomState &g = c.g;
+    const int P = c.P;
+    // the depth sort's last pass also writes the tile counts in depth order, so the instance scan reads them
+    // coalesced instead of gathering them through the order (the expansion records it leaves to the expansion's gather
+    // by rank: writing them too measured slower, cfg 5 depth sort 0.232 -> 0.352 ms for expand 0.241 -> 0.221 ms,
+    // profiles/r6t_libab_sort_gather_cfg5.txt)
+    SortGather ga;
+    ga.src = g.tiles; ga.dst = g.tiles_sorted;
+    // Relative depth keys ("depth_rel" 1) where the sort takes the multi-kernel path: the kept keys span
+    // kmax - kmin, so rs_rel_key maps them onto [0, span] and the culled ones onto span + 1, and the sort runs
+    // ceil(bits / 9) passes instead of 4 (cfg 5: 26 bits, 3 passes of 9 bits)
+    int rel_bits = 32;
+    const uint32_t os_max = (uint32_t)tuning("onesweep_max_n", 3 << 20);
+    if (tuning("depth_rel", 1) && c.kmin <= c.kmax && (uint32_t)P > os_max && c.kmax - c.kmin < 0xfffffffeu)
+        rel_bits = 32 - __builtin_clz(c.kmax - c.kmin + 1);
+    gsr_set_tuning("stat_depth_passes", rel_bits <= 27 ? (rel_bits + 8) / 9 : 4);
+    if (rel_bits <= 27)
+        GSR_STAGE(ST_DEPTH_SORT, c.dbg,
+                  launch_depth_sort_rel(stream, g.sort, (uint32_t)P, g.depth_key, c.kmin, c.kmax - c.kmin + 1, rel_bits,
+                                        &ga));
+    else
+        GSR_STAGE(ST_DEPTH_SORT, c.dbg, launch_radix_sort(stream, g.sort, (uint32_t)P, 32, false, g.depth_key, &ga));
+    GSR_STAGE(ST_SCAN, c.dbg,
+              launch_exclusive_scan_lookback(stream, g.tiles_sorted, nullptr, (uint32_t)P, g.inst_off, g.scan_status,
+                                             g.counters + CNT_SCAN_TICKET, g.counters + CNT_OVERFLOW));
+    return GSR_OK;
+}
+
+// The binning buffer for R instances: the one requested before the wait if it is large enough, else a new one.  The
+// total becomes the next call's hint here, after the wait and on the success path only.
+static int fwd_binning_buffer(FwdCall &c) {
+    readback_hint(c.dev) = c.R;
+    if (!c.bin || (int64_t)c.R > c.bin_cap) {
+        c.bin = c.alloc(c.alloc_ctx, GSR_BUF_BINNING, carve_binning(nullptr, c.R, c.T, c.b));
+        if (!c.bin) return fail(GSR_ERR_ALLOC, "binning buffer allocation failed");
     }
-    carve_binning(bin, R, T, b);  // offsets from R: a larger buffer only has unused space at the end
-    if ((uint64_t)RS_BINS * div_up(R ? R : 1, RS_TILE) + 1 > (uint64_t)SCAN_TILE * SCAN_MAX_BLOCKS)
+    carve_binning(c.bin, c.R, c.T, c.b);  // offsets from R: a larger buffer only has unused space at the end
+    if ((uint64_t)RS_BINS * div_up(c.R ? c.R : 1, RS_TILE) + 1 > (uint64_t)SCAN_TILE * SCAN_MAX_BLOCKS)
         return fail(GSR_ERR_OVERFLOW, "too many tile instances for the single-level scan");
-    if (bucket) {
-        if (R > 0) {
-            bp.keys = b.bk_keys; bp.inst_gid = b.inst_gid; bp.inv = b.inv; bp.R = R;
-            // region scatter: keys into 16-tile regions first (long runs per block), then a partition pass into the tile
-            // buckets (gsr_bin.hip bk_partition_kernel) -- "bk_region" 1 (default) above 4096 tiles (short runs: cfg 3 has
-            // ~2 keys per block and tile), 2 always, 0 never (at 800x800, 2500 tiles, the direct scatter's 12 us is
-            // already below the partition pass alone)
-            const int bkr = tuning("bk_region", 1);
-            // (the tile-in-region rides in u's top bits: R <= 2^28; the automatic choice also wants >= 256 keys per region
-            // on average, so that a partition chunk rarely spans more regions than its LDS bins cover)
-            const uint32_t nreg = div_up(T, BK_REGION);
-            bp.keys_reg = ((bkr == 2 || (bkr == 1 && T > 4096 && R >= 256u * nreg)) && R <= (1u << BK_REG_SHIFT))
-                              ? b.bk_keys2 : nullptr;
-            bp.order = lpt ? im.order_fwd : nullptr;
-            // per-XCD LPT orders for the whole-tile composites ("xcd_lpt" 1, with the backward's bucket lists)
-            xcd_fwd = lpt && lpt_append_range(T) && tuning("lpt_append", 1) && tuning("xcd_lpt", 1) &&
-                      render_fwd_parts((int)T) == 1;
-            bp.order_xcd = xcd_fwd ? im.order_xcd : nullptr;
-            bp.lpt_shift = tuning("lpt_shift", 3);
-            GSR_STAGE(ST_BK_SCATTER, dbg, launch_bucket_scatter(stream, bp));  // and the forward LPT order
-            SegSortParams sp;
-            // the long tiles lead the LPT order only while SEG_CAP + 1 is a multiple of the bucket width
-            sp.T = T; sp.ranges = im.ranges;
-            sp.tile_order = (lpt && (((SEG_CAP + 1) >> tuning("lpt_shift", 3)) << tuning("lpt_shift", 3)) == SEG_CAP + 1)
-                                ? im.order_fwd : nullptr; sp.keys = b.bk_keys; sp.keys2 = b.bk_keys2;
-            sp.sorted_u = b.sorted_u; sp.long_list = im.bk_long_list; sp.long_cnt = g.counters + CNT_LONG;
-            // (Round 4's prefix binning -- radix-select each long bucket's 512 front-most keys, sort only those, and
-            // let render_fwd extend a walk that outlives them -- measured slower at cfg 3, seg_sort 0.053 -> 0.060 ms
-            // and render_fwd 0.171 -> 0.176 ms, and was removed in round 5: DESIGN.md appendix)
-            GSR_STAGE(ST_SEG_SORT, dbg, launch_seg_sort(stream, sp));
-        } else {
-            GSR_HIP(hipMemsetAsync(im.ranges, 0, sizeof(uint2) * T, stream));
-            if (lpt) launch_tile_order(stream, im.ranges, nullptr, 0, (int)T, im.order_fwd, im.lpt_hist);
-        }
-    } else {
-        bool keys16 = false;
-        if (R > 0) {
-            ExpandParams ep;
-            ep.P = (uint32_t)P; ep.R = R; ep.gx = gx; ep.gy = gy;
-            ep.order = g.order; ep.inst_off = g.inst_off; ep.tiles = g.tiles; ep.exp_rec = g.exp_rec;
-            ep.exp_sorted = sorted_exp ? g.exp_sorted : nullptr;
-            ep.exp_owner = b.exp_owner;
-            // 16-bit tile keys up to 65536 tiles ("tile_key16" 0: 32-bit): the tile sort, the expansion's key stores and
-            // the range search move 2 bytes per key instead of 4
-            const TileSortPlan plan = tile_sort_plan(T);
-            const bool k16 = plan.k16;
-            ep.keys_out = k16 ? nullptr : b.sort.k[0];
-            ep.keys16_out = k16 ? reinterpret_cast<uint16_t *>(b.sort.k[0]) : nullptr;
-            ep.inst_gid = b.inst_gid; ep.inst_start = g.inst_start; ep.inv_none = b.inv;
-            GSR_STAGE(ST_EXPAND, dbg, launch_expand(stream, ep));
-            if (k16)
-                GSR_STAGE(ST_TILE_SORT, dbg, launch_radix_sort16(stream, b.sort, R, plan.digit_bits, plan.passes, tile_key_bits(T)));
-            else
-                GSR_STAGE(ST_TILE_SORT, dbg,
-                          launch_radix_sort(stream, b.sort, R, tile_key_bits(T), false, nullptr, nullptr,
-                                            &tile_onesweep));
-            keys16 = k16;
-        }
-        GSR_STAGE(ST_RANGES, dbg, {
-            GSR_HIP(hipMemsetAsync(im.ranges, 0, sizeof(uint2) * T, stream));
-            if (keys16) launch_identify_ranges16(stream, reinterpret_cast<const uint16_t *>(b.keys_sorted), R, im.ranges);
-            else launch_identify_ranges(stream, b.keys_sorted, R, im.ranges);
-        });
+    return GSR_OK;
+}
+
+// Bucket binning: the scatter into the tile buckets (and the forward LPT orders), then the per-tile sorts
+static int fwd_bin_bucket(FwdCall &c) {
+    hipStream_t stream = c.stream;
+    const GeomState &g = c.g;
+    const BinningState &b = c.b;
+    const ImageState &im = c.im;
+    const uint32_t T = c.T, R = c.R;
+    const int lpt = c.lpt;
+    if (R == 0) {
+        GSR_HIP(hipMemsetAsync(im.ranges, 0, sizeof(uint2) * T, stream));
         if (lpt) launch_tile_order(stream, im.ranges, nullptr, 0, (int)T, im.order_fwd, im.lpt_hist);
+        return GSR_OK;
     }
+    BucketParams &bp = c.bp;
+    bp.keys = b.bk_keys; bp.inst_gid = b.inst_gid; bp.inv = b.inv; bp.R = R;
+    // region scatter: keys into 16-tile regions first (long runs per block), then a partition pass into the tile
+    // buckets (gsr_bin.hip bk_partition_kernel) -- "bk_region" 1 (default) above 4096 tiles (short runs: cfg 3 has
+    // ~2 keys per block and tile), 2 always, 0 never (at 800x800, 2500 tiles, the direct scatter's 12 us is
+    // already below the partition pass alone)
+    const int bkr = tuning("bk_region", 1);
+    // (the tile-in-region rides in u's top bits: R <= 2^28; the automatic choice also wants >= 256 keys per region
+    // on average, so that a partition chunk rarely spans more regions than its LDS bins cover)
+    const uint32_t nreg = div_up(T, BK_REGION);
+    bp.keys_reg = ((bkr == 2 || (bkr == 1 && T > 4096 && R >= 256u * nreg)) && R <= (1u << BK_REG_SHIFT))
+                      ? b.bk_keys2 : nullptr;
+    bp.order = lpt ? im.order_fwd : nullptr;
+    // per-XCD LPT orders for the whole-tile composites ("xcd_lpt" 1, with the backward's bucket lists)
+    c.xcd_fwd = lpt && lpt_append_range(T) && tuning("lpt_append", 1) && tuning("xcd_lpt", 1) &&
+                render_fwd_parts((int)T) == 1;
+    bp.order_xcd = c.xcd_fwd ? im.order_xcd : nullptr;
+    bp.lpt_shift = tuning("lpt_shift", 3);
+    GSR_STAGE(ST_BK_SCATTER, c.dbg, launch_bucket_scatter(stream, bp));  // and the forward LPT order
+    SegSortParams sp;
+    // the long tiles lead the LPT order only while SEG_CAP + 1 is a multiple of the bucket width
+    sp.T = T; sp.ranges = im.ranges;
+    sp.tile_order = (lpt && (((SEG_CAP + 1) >> tuning("lpt_shift", 3)) << tuning("lpt_shift", 3)) == SEG_CAP + 1)
+                        ? im.order_fwd : nullptr;
+    sp.keys = b.bk_keys; sp.keys2 = b.bk_keys2;
+    sp.sorted_u = b.sorted_u; sp.long_list = im.bk_long_list; sp.long_cnt = g.counters + CNT_LONG;
+    GSR_STAGE(ST_SEG_SORT, c.dbg, launch_seg_sort(stream, sp));
+    return GSR_OK;
+}
+
+// Radix binning: the depth-ordered expansion, the stable tile sort and the tile ranges
+static int fwd_bin_radix(FwdCall &c) {
+    hipStream_t stream = c.stream;
+    const GeomState &g = c.g;
+    BinningState &b = c.b;
+    const ImageState &im = c.im;
+    const uint32_t T = c.T, R = c.R;
+    bool keys16 = false;
+    if (R > 0) {
+        ExpandParams ep;
+        ep.P = (uint32_t)c.P; ep.R = R; ep.gx = c.gx; ep.gy = c.gy;
+        ep.order = g.order; ep.inst_off = g.inst_off; ep.tiles = g.tiles; ep.exp_rec = g.exp_rec;
+        ep.exp_sorted = nullptr;  // the depth sort leaves the records in place: gathered by rank
+        ep.exp_owner = b.exp_owner;
+        // 16-bit tile keys up to 65536 tiles ("tile_key16" 0: 32-bit): the tile sort, the expansion's key stores and
+        // the range search move 2 bytes per key instead of 4
+        const TileSortPlan plan = tile_sort_plan(T);
+        keys16 = plan.k16;
+        ep.keys_out = keys16 ? nullptr : b.sort.k[0];
+        ep.keys16_out = keys16 ? reinterpret_cast<uint16_t *>(b.sort.k[0]) : nullptr;
+        ep.inst_gid = b.inst_gid; ep.inst_start = g.inst_start; ep.inv_none = b.inv;
+        GSR_STAGE(ST_EXPAND, c.dbg, launch_expand(stream, ep));
+        if (keys16)
+            GSR_STAGE(ST_TILE_SORT, c.dbg,
+                      launch_radix_sort16(stream, b.sort, R, plan.digit_bits, plan.passes, tile_key_bits(T)));
+        else
+            GSR_STAGE(ST_TILE_SORT, c.dbg, launch_radix_sort(stream, b.sort, R, tile_key_bits(T)));
+    }
+    GSR_STAGE(ST_RANGES, c.dbg, {
+        GSR_HIP(hipMemsetAsync(im.ranges, 0, sizeof(uint2) * T, stream));
+        if (keys16) launch_identify_ranges16(stream, reinterpret_cast<const uint16_t *>(b.keys_sorted), R, im.ranges);
+        else launch_identify_ranges(stream, b.keys_sorted, R, im.ranges);
+    });
+    if (c.lpt) launch_tile_order(stream, im.ranges, nullptr, 0, (int)T, im.order_fwd, im.lpt_hist);
+    return GSR_OK;
+}
+
+// The composite: colour, inverse depth, alpha, and the state the backward and the replays read
+static int fwd_composite(FwdCall &c) {
+    gsr_forward_args *a = c.a;
+    hipStream_t stream = c.stream;
+    const GeomState &g = c.g;
+    const BinningState &b = c.b;
+    const ImageState &im = c.im;
+    const uint32_t T = c.T;
+    const int lpt = c.lpt;
     // split heavy tiles combine tile_last / tile_loaded with atomicMax: start from zero (adjacent arrays; the
     // bucket path's column pass clears them)
-    if (!bucket || R == 0)
+    if (!c.bucket || c.R == 0)
         GSR_HIP(hipMemsetAsync(im.tile_last, 0,
                                (size_t)(reinterpret_cast<char *>(im.lpt_bcnt + LPT_BCNT_WORDS) -
                                         reinterpret_cast<char *>(im.tile_last)),
                                stream));
     RenderFwdParams rp;
-    rp.W = W; rp.H = H; rp.gx = gx; rp.gy = gy; rp.num_tiles = (int)T;
-    rp.tile_order = lpt ? (xcd_fwd ? im.order_xcd : im.order_fwd) : nullptr;
-    rp.xcd = xcd_fwd ? 1 : 0;
+    rp.W = c.W; rp.H = c.H; rp.gx = c.gx; rp.gy = c.gy; rp.num_tiles = (int)T;
+    rp.tile_order = lpt ? (c.xcd_fwd ? im.order_xcd : im.order_fwd) : nullptr;
+    rp.xcd = c.xcd_fwd ? 1 : 0;
     rp.ranges = im.ranges; rp.sorted_u = b.sorted_u; rp.inst_gid = b.inst_gid;
     rp.point_list = b.point_list; rp.tile_loaded = im.tile_loaded;
     rp.inv = b.inv;
     rp.rec = g.rec;
-    rp.bg = a->background ? a->background : e.background_image;
-    rp.bg_image = e.background_image; rp.out_alpha = e.out_alpha;
+    rp.bg = a->background ? a->background : c.e.background_image;
+    rp.bg_image = c.e.background_image; rp.out_alpha = c.e.out_alpha;
     rp.out_color = a->out_color; rp.out_invdepth = a->out_invdepth; rp.final_T = im.final_T;
     rp.n_contrib = im.n_contrib; rp.tile_last = im.tile_last;
     // checkpoints for the segmented backward ("bwd_seg" 1, spacing "seg_k" instances: 32 or a multiple of 64) while the image
@@ -851,22 +964,64 @@ int gsr_forward_features(gsr_forward_args *a, const gsr_composite_ext *ext, cons
         const int k = tuning("seg_k", 64);  // cfg 2: 32 / 64 / 128 -> render_bwd 0.106 / 0.107 / 0.129 ms, render_fwd 0.070 / 0.065 / 0.062
         rp.ck_k = k <= 32 ? 32u : (uint32_t)(k / 64) * 64u;
     }
-    if (R > 0 && (!rp.point_list || !rp.inst_gid || !rp.sorted_u))
+    if (c.R > 0 && (!rp.point_list || !rp.inst_gid || !rp.sorted_u))
         return fail(GSR_ERR_ARG, "internal: composite buffer not set");
-    GSR_STAGE(ST_RENDER_FWD, dbg, launch_render_fwd(stream, rp));
-    if (fx.given) {  // the feature image, replayed from what the composite just recorded (tile_last = 0: zeros)
-        FeatFwdParams fp;
-        fp.W = W; fp.H = H; fp.gx = gx; fp.gy = gy; fp.num_tiles = (int)T; fp.C = fx.C;
-        fp.ranges = im.ranges; fp.point_list = b.point_list; fp.n_contrib = im.n_contrib; fp.tile_last = im.tile_last;
-        fp.rec = g.rec; fp.features = fx.features; fp.out = fx.out_features; fp.strip_exact = 1;
-        GSR_STAGE(ST_FEAT_FWD, dbg, launch_feat_fwd(stream, fp));
-    }
-    (void)depth_onesweep;
-    (void)tile_onesweep;
-    if (dbg)  // every radix sort clears its error word (onesweep: with its control block; multi-kernel: pass 0)
-        return check_lookback_flags(stream, device_guard.dev, g.counters, bucket ? nullptr : g.sort.ctrl + RS_CTRL_ERR,
-                                    bucket || R == 0 ? nullptr : b.sort.ctrl + RS_CTRL_ERR);
+    GSR_STAGE(ST_RENDER_FWD, c.dbg, launch_render_fwd(stream, rp));
     return GSR_OK;
+}
+
+// The feature image, replayed from what the composite just recorded (tile_last = 0: zeros)
+static int fwd_features(FwdCall &c) {
+    hipStream_t stream = c.stream;
+    FeatFwdParams fp;
+    fp.src = replay_src(c);
+    fp.C = c.fx.C; fp.features = c.fx.features; fp.out = c.fx.out_features;
+    GSR_STAGE(ST_FEAT_FWD, c.dbg, launch_feat_fwd(stream, fp));
+    return GSR_OK;
+}
+
+int gsr_forward(gsr_forward_args *a, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr,
+                int64_t *num_rendered) {
+    return gsr_forward_ext(a, nullptr, alloc, alloc_ctx, stream_ptr, num_rendered);
+}
+
+int gsr_forward_ext(gsr_forward_args *a, const gsr_composite_ext *ext, gsr_alloc_fn alloc, void *alloc_ctx,
+                    void *stream_ptr, int64_t *num_rendered) {
+    return gsr_forward_features(a, ext, nullptr, alloc, alloc_ctx, stream_ptr, num_rendered);
+}
+
+int gsr_forward_features(gsr_forward_args *a, const gsr_composite_ext *ext, const gsr_features_ext *feat,
+                         gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr, int64_t *num_rendered) {
+    if (!a || !alloc || !num_rendered) return fail(GSR_ERR_ARG, "null argument");
+    FwdCall c{};
+    c.a = a; c.alloc = alloc; c.alloc_ctx = alloc_ctx;
+    c.stream = (hipStream_t)stream_ptr; c.dbg = a->debug != 0;
+    int rc = fwd_check_args(c, ext, feat);
+    if (rc) return rc;
+    // Both live in this frame across every stage: the stream's device stays current until the call returns, and an
+    // early return of any stage after the preprocess launch runs ~InflightReadback (a wait for the stream) before
+    // this thread's pinned words can be reused.  Destroyed in this order: the wait, then the device restored.
+    StreamDeviceGuard device_guard(c.stream);
+    InflightReadback inflight;
+    c.dev = device_guard.dev;
+    c.inflight = &inflight;
+    *num_rendered = 0;
+    a->num_big_out = 0;
+    if (c.P == 0) return fwd_empty_scene(c);
+    rc = fwd_preprocess(c);
+    if (!rc) rc = fwd_readback(c);
+    if (rc) return rc;
+    *num_rendered = c.R;
+    a->num_big_out = c.nbig;
+    if (!c.bucket) rc = fwd_depth_sort(c);
+    if (!rc) rc = fwd_binning_buffer(c);
+    if (!rc) rc = c.bucket ? fwd_bin_bucket(c) : fwd_bin_radix(c);
+    if (!rc) rc = fwd_composite(c);
+    if (!rc && c.fx.given) rc = fwd_features(c);
+    if (rc || !c.dbg) return rc;
+    // every radix sort clears its error word (onesweep: with its control block; multi-kernel: pass 0)
+    return check_lookback_flags(c.stream, c.dev, c.g.counters, c.bucket ? nullptr : c.g.sort.ctrl + RS_CTRL_ERR,
+                                c.bucket || c.R == 0 ? nullptr : c.b.sort.ctrl + RS_CTRL_ERR);
 }
 
 // The per-Gaussian outputs preprocess_bwd writes for Gaussians [g0, g1), as zero-fill segments of the composite backward
@@ -940,9 +1095,9 @@ static int background_grads(const gsr_backward_args *a, const CompositeExt &e, c
     return GSR_OK;
 }
 
-// One backward call's state: what the argument checks read and derived, the carved buffers, and what one stage leaves
-// for the next.  Each stage below takes it whole.
-struct BwdCall {
+// One backward call's state: what the argument checks read and derived, the forward's state recovered from its buffers,
+// and what one stage leaves for the next.  Each stage below takes it whole.
+struct BwdCall : RasterState {
     const gsr_backward_args *a;
     gsr_alloc_fn alloc;
     void *alloc_ctx;
@@ -953,16 +1108,6 @@ struct BwdCall {
     FeaturesExt fx;
     bool feat_bwd;   // the feature work of this call: only with an upstream gradient of the feature image
     int64_t g0, g1;  // the Gaussians of the per-Gaussian stage
-    int gx, gy;
-    uint32_t T, R;
-    // num_big < 0: not known on the host (the upstream backward signature has no such argument, gsr_torch_ext): nbig
-    // is then the most there can be (each has > BIG_GAUSSIAN_TILES instances), which sizes the sums, and nbig_dev the
-    // count the preprocess left in the geometry buffer, which the reductions read; else nbig is exact, nbig_dev null
-    uint32_t nbig;
-    const uint32_t *nbig_dev;
-    GeomState g;
-    BinningState b;
-    ImageState im;
     BwdScratch sc;
     GatherSrc src;   // what every gather of this call tests (live: null with "bwd_live" 0, decided once)
     bool prezeroed;  // the composite zero-filled the per-Gaussian outputs (zero_fill_plan), and did launch
@@ -1017,14 +1162,7 @@ static int bwd_check_args(BwdCall &c, const gsr_composite_ext *ext, const gsr_ab
 // The forward's buffers and this call's scratch (allocated here, or the composite call's for GSR_BWD_GAUSSIANS), carved
 static int bwd_carve(BwdCall &c) {
     const gsr_backward_args *a = c.a;
-    c.gx = (a->W + BLOCK_X - 1) / BLOCK_X, c.gy = (a->H + BLOCK_Y - 1) / BLOCK_Y;
-    c.T = (uint32_t)(c.gx * c.gy);
-    c.R = (uint32_t)a->R;
-    carve_geom(a->geom_buffer, a->P, c.g);
-    carve_binning(a->binning_buffer, c.R, c.T, c.b);
-    carve_image(a->image_buffer, a->W, a->H, c.im);
-    c.nbig = a->num_big < 0 ? c.R / (BIG_GAUSSIAN_TILES + 1) + 1 : (uint32_t)a->num_big;
-    c.nbig_dev = a->num_big < 0 ? c.g.counters + CNT_BIG : nullptr;
+    recover_state(c, a->P, a->W, a->H, a->R, a->num_big, a->geom_buffer, a->binning_buffer, a->image_buffer);
     const bool abs = c.ab.dL_dmeans2D_abs != nullptr;
     const int fb = c.feat_bwd ? feat_block(c.fx.C) : 0;
     char *scratch = a->bwd_scratch;
@@ -1033,10 +1171,7 @@ static int bwd_carve(BwdCall &c) {
         if (!scratch) return fail(GSR_ERR_ALLOC, "backward scratch allocation failed");
     }
     carve_bwd_scratch(scratch, c.R, c.nbig, abs, fb, c.sc);
-    c.src.radii = a->radii; c.src.tiles = c.g.tiles; c.src.inst_start = c.g.inst_start;
-    c.src.big_slot = c.g.big_slot; c.src.big_list = c.g.big_list; c.src.inv = c.b.inv;
-    c.src.live = tuning("bwd_live", 1) ? c.g.live : nullptr;
-    c.src.live_valid = c.g.counters + CNT_LIVE_VALID;
+    c.src = gather_src(a->radii, c, true, tuning("bwd_live", 1) != 0);
     return GSR_OK;
 }
 
@@ -1089,12 +1224,11 @@ static int bwd_features(BwdCall &c) {
     const gsr_backward_args *a = c.a;
     hipStream_t stream = c.stream;
     FeatBwdParams fp;
-    fp.W = a->W; fp.H = a->H; fp.gx = c.gx; fp.gy = c.gy; fp.num_tiles = (int)c.T; fp.C = c.fx.C;
-    fp.ranges = c.im.ranges; fp.point_list = c.b.point_list; fp.n_contrib = c.im.n_contrib;
-    fp.tile_last = c.im.tile_last; fp.tile_loaded = c.im.tile_loaded; fp.sorted_u = c.b.sorted_u;
-    fp.rec = c.g.rec; fp.final_T = c.im.final_T; fp.features = c.fx.features; fp.dL_dF = c.fx.dL_dout_features;
+    fp.src = replay_src(c);
+    fp.C = c.fx.C;
+    fp.final_T = c.im.final_T; fp.features = c.fx.features; fp.dL_dF = c.fx.dL_dout_features;
     fp.rows = c.sc.rows; fp.frows = c.sc.feat_rows;
-    fp.live = c.src.live ? c.g.live : nullptr; fp.strip_exact = 1;
+    fp.live = c.src.live ? c.g.live : nullptr;
     FeatGatherParams gp;
     gp.P = a->P; gp.C = c.fx.C;
     gp.src = c.src;
@@ -1269,31 +1403,20 @@ int gsr_contributions(const gsr_contrib_args *x, gsr_alloc_fn alloc, void *alloc
         if (wmax) GSR_HIP(hipMemsetAsync(wmax, 0, sizeof(float) * (size_t)P, stream));
         return GSR_OK;
     }
-    const int gx = (W + BLOCK_X - 1) / BLOCK_X, gy = (H + BLOCK_Y - 1) / BLOCK_Y;
-    const uint32_t T = (uint32_t)(gx * gy);
-    GeomState g;
-    BinningState b;
-    ImageState im;
-    carve_geom(static_cast<char *>(const_cast<void *>(geom)), P, g);
-    carve_binning(static_cast<char *>(const_cast<void *>(binning)), R, T, b);
-    carve_image(static_cast<char *>(const_cast<void *>(image)), W, H, im);
+    RasterState st;
+    recover_state(st, P, W, H, R, num_big, geom, binning, image);
     char *scratch = alloc(alloc_ctx, GSR_BUF_CONTRIB_SCRATCH, gsr_contrib_scratch_bytes(R, num_big));
     if (!scratch) return fail(GSR_ERR_ALLOC, "contribution scratch allocation failed");
     uint4 *rows, *bigsum;
     carve_contrib_scratch(scratch, R, num_big, &rows, &bigsum);
     ContribWalkParams wp;
-    wp.W = W; wp.H = H; wp.gx = gx; wp.gy = gy; wp.num_tiles = (int)T;
-    wp.ranges = im.ranges; wp.point_list = b.point_list; wp.n_contrib = im.n_contrib;
-    wp.tile_last = im.tile_last; wp.tile_loaded = im.tile_loaded; wp.sorted_u = b.sorted_u;
-    wp.rec = g.rec; wp.pixel_weights = in.get(&gsr_contrib_args::pixel_weights); wp.rows = rows; wp.strip_exact = 1;
+    wp.src = replay_src(st);
+    wp.pixel_weights = in.get(&gsr_contrib_args::pixel_weights); wp.rows = rows;
     ContribGatherParams gp;
     gp.P = P;
-    gp.src.radii = radii; gp.src.tiles = g.tiles; gp.src.inst_start = g.inst_start;
-    gp.src.big_slot = g.big_slot; gp.src.big_list = g.big_list; gp.src.inv = b.inv;
-    gp.src.live = nullptr; gp.src.live_valid = nullptr;  // the backward composite's: not valid here
+    gp.src = gather_src(radii, st, false, false);  // the live flags are the backward composite's: not valid here
     gp.rows = rows; gp.bigsum = bigsum;
-    gp.nbig = num_big < 0 ? (uint32_t)(R / (BIG_GAUSSIAN_TILES + 1) + 1) : (uint32_t)num_big;
-    gp.nbig_dev = num_big < 0 ? g.counters + CNT_BIG : nullptr;
+    gp.nbig = st.nbig; gp.nbig_dev = st.nbig_dev;
     gp.count = count; gp.wsum = wsum; gp.wmax = wmax; gp.accumulate = accumulate;
     GSR_STAGE(ST_CONTRIB_WALK, false, launch_contrib_walk(stream, wp));
     GSR_STAGE(ST_CONTRIB_GATHER, false, {

@@ -4,9 +4,9 @@
 // Taming-3DGS: the hit count, error-based densification: the sum under a per-pixel error m); no gradient is involved.
 //
 // Kernels of their own beside the composites and the feature kernels, so a call that does not ask for the statistics
-// launches exactly what it launched before.  They only READ what the colour forward recorded (point_list, ranges,
-// n_contrib, tile_last / tile_loaded, sorted_u, inv, the 48-B render records) and write a scratch buffer of this call
-// and the three outputs: a backward on the same state afterwards is untouched.
+// launches exactly what it launched before.  They only READ what the colour forward recorded (ReplaySrc for the walk,
+// GatherSrc's inv for the gather) and write a scratch buffer of this call and the three outputs: a backward on the
+// same state afterwards is untouched.
 //
 // Pixels -> Gaussians without float atomics, as the backward does it: the walk reduces each instance's pairs inside its
 // wave (the sum by a fixed DPP tree) into the instance's 16-B row, stored by expansion index, so a Gaussian's rows are
@@ -32,82 +32,56 @@ __device__ __forceinline__ uint32_t wave_umax(uint32_t v) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// The walk: one wave per tile, 4 pixels per lane, front to back over point_list[ranges[tile]] up to tile_last, the
-// records staged in LDS batches as feat_fwd_kernel stages them; T restarts from 1 and follows the forward's
-// T (1 - alpha), the pair test is feat_fwd_kernel's (sorted index below n_contrib, the composite's alpha decision), so
-// the weights are the colour render's own.  A pixel whose weight m is not > 0 is left out of everything (its
-// n_contrib is read as 0).  Per instance that a pixel takes: the count from the strips' ballots, the lane's sum over
-// its 4 pixels in strip order and then wave_sum's fixed tree, the max as integers; lane j of the batch keeps instance
-// j's three values and stores its row once.  Every instance the forward loaded gets a row: [tile_last, tile_loaded)
-// zeros.
+// The walk: one wave per tile, 4 pixels per lane, front to back over point_list[ranges[tile]] up to tile_last, built
+// from the replay pieces of gsr_replay.h (the batches staged in LDS, the pair test: sorted index below n_contrib and
+// the composite's alpha decision); T restarts from 1 and follows the forward's T (1 - alpha), so the weights are the
+// colour render's own.  A pixel whose weight m is not > 0 is left out of everything (its n_contrib is read as 0).  Per
+// instance that a pixel takes: the count from the strips' ballots, the lane's sum over its 4 pixels in strip order and
+// then wave_sum's fixed tree, the max as integers; lane j of the batch keeps instance j's three values and stores its
+// row once.  Every instance the forward loaded gets a row: [tile_last, tile_loaded) zeros.
 // ------------------------------------------------------------------------------------------------
 template <bool GUARD>
 __global__ __launch_bounds__(64) void contrib_walk_kernel(ContribWalkParams p) {
-    __shared__ FwdRec s_rec[FEAT_BATCH];
-    __shared__ uint32_t s_gid[FEAT_BATCH];
+    __shared__ FwdRec s_rec[REPLAY_BATCH];
+    __shared__ uint32_t s_gid[REPLAY_BATCH];
     const int lane = threadIdx.x;
-    const int tile = blockIdx.x;
-    const int tx = tile % p.gx, ty = tile / p.gx;
-    const int px = tx * BLOCK_X + (lane & 15);
-    const int py0 = ty * BLOCK_Y + (lane >> 4);
-    const float pfx = (float)px;
-    const float row0 = (float)(ty * BLOCK_Y), col0 = (float)(tx * BLOCK_X);
-    const uint32_t r0 = __builtin_amdgcn_readfirstlane(p.ranges[tile].x);
-    const uint32_t tl = __builtin_amdgcn_readfirstlane(p.tile_last[tile]);
-    const uint32_t loaded = __builtin_amdgcn_readfirstlane(p.tile_loaded[tile]);
+    const ReplayTile t = replay_tile(p.src, (int)blockIdx.x, lane);
     // the instances the forward loaded but no pixel reached
-    for (uint32_t e = tl + (uint32_t)lane; e < loaded; e += 64) p.rows[p.sorted_u[r0 + e]] = make_uint4(0, 0, 0, 0);
-    if (tl == 0) return;
+    for (uint32_t e = t.tl + (uint32_t)lane; e < t.loaded; e += 64)
+        p.rows[p.src.sorted_u[t.r0 + e]] = make_uint4(0, 0, 0, 0);
+    if (t.tl == 0) return;
 
-    float T[PIX_PER_LANE], prow[PIX_PER_LANE], mw[PIX_PER_LANE];
-    uint32_t lastc[PIX_PER_LANE];
+    ReplayPixel q[PIX_PER_LANE];
+    float T[PIX_PER_LANE], mw[PIX_PER_LANE];
 #pragma unroll
     for (int k = 0; k < PIX_PER_LANE; k++) {
-        const int py = py0 + 4 * k;
-        const bool inside = px < p.W && py < p.H;
-        const size_t pid = inside ? (size_t)py * p.W + px : 0;
-        mw[k] = (inside && p.pixel_weights) ? p.pixel_weights[pid] : 1.0f;
-        lastc[k] = (inside && mw[k] > 0.0f) ? p.n_contrib[pid] : 0u;
+        q[k] = replay_pixel(p.src, t, k);
+        mw[k] = (q[k].inside && p.pixel_weights) ? p.pixel_weights[q[k].pid] : 1.0f;
+        // own read under the weight's mask: replay_pixel's, then a select, ran 3 % slower (replay_path_resources.md)
+        q[k].lastc = (q[k].inside && mw[k] > 0.0f) ? p.src.n_contrib[q[k].pid] : 0u;
         T[k] = 1.0f;
-        prow[k] = (float)py;
     }
-    for (uint32_t b0 = 0; b0 < tl; b0 += FEAT_BATCH) {
-        const int cnt = (int)min((uint32_t)FEAT_BATCH, tl - b0);
-        float4 ra, rb;
-        const uint32_t s_me = r0 + b0 + (uint32_t)lane;
-        const uint32_t my_m = feat_stage(p.rec, p.point_list, s_me, lane < cnt, lane, s_rec, s_gid, p.strip_exact != 0,
-                                         row0, col0, ra, rb);
-        const uint32_t my_row = lane < cnt ? p.sorted_u[s_me] : 0u;
-        uint64_t sk[PIX_PER_LANE], un = 0;
-#pragma unroll
-        for (int k = 0; k < PIX_PER_LANE; k++) {
-            sk[k] = __ballot((my_m >> k) & 1u);
-            un |= sk[k];
-        }
-        wave_lds_sync();
+    for (uint32_t b0 = 0; b0 < t.tl; b0 += REPLAY_BATCH) {
+        const int cnt = (int)min((uint32_t)REPLAY_BATCH, t.tl - b0);
+        ReplayBatch bt = replay_batch(p.src, t, t.r0 + b0, +1, cnt, lane, s_rec, s_gid);
         uint32_t my_cnt = 0, my_max = 0;  // instance `lane` of the batch
         float my_sum = 0.f;
-        while (un) {  // the instances that reach a strip, front to back
-            const int j = (int)__builtin_ctzll(un);
-            un &= ~(1ull << j);
-            const uint32_t idx = b0 + (uint32_t)j;
-            const float4 a = s_rec[j].a, b = s_rec[j].b;  // a: x, y, A, B; b: C, o, -, -
-            const float dx = a.x - pfx;
-            const float P0 = (a.z * dx) * dx, L = a.w * dx;
+        while (bt.un) {  // the instances that reach a strip, front to back
+            const int j = (int)__builtin_ctzll(bt.un);
+            bt.un &= ~(1ull << j);
+            const ReplayInst in = replay_inst(s_rec, s_gid, j, t.pfx);
             uint32_t c = 0;  // wave-uniform
             float ls = 0.f, lm = 0.f;
 #pragma unroll
             for (int k = 0; k < PIX_PER_LANE; k++) {
-                if (!((sk[k] >> j) & 1u)) continue;  // wave-uniform
-                const float power2 = power2_at(b.x, a.y - prow[k], P0, L);
-                const float alpha = fminf(0.99f, b.y * __builtin_amdgcn_exp2f(power2));
-                const bool pass = idx < lastc[k] && feat_alpha_pass<GUARD>(power2, alpha, p.rec, s_gid[j], pfx, prow[k]);
-                c += (uint32_t)__popcll(__ballot(pass));
-                if (pass) {
-                    const float v = mw[k] * (alpha * T[k]);  // m == 1 without an image: the weight's own bits
+                if (!((bt.sk[k] >> j) & 1u)) continue;  // wave-uniform
+                const ReplayPair pr = replay_pair<GUARD>(p.src, in, b0 + (uint32_t)j, q[k], t.pfx);
+                c += (uint32_t)__popcll(__ballot(pr.pass));
+                if (pr.pass) {
+                    const float v = mw[k] * (pr.alpha * T[k]);  // m == 1 without an image: the weight's own bits
                     ls += v;
                     lm = fmaxf(lm, v);
-                    T[k] = T[k] * (1 - alpha);
+                    T[k] = T[k] * (1 - pr.alpha);
                 }
             }
             if (c) {  // wave-uniform: every lane takes part in the reductions
@@ -116,18 +90,14 @@ __global__ __launch_bounds__(64) void contrib_walk_kernel(ContribWalkParams p) {
                 if (lane == j) my_cnt = c, my_sum = s, my_max = m;
             }
         }
-        if (lane < cnt) p.rows[my_row] = make_uint4(my_cnt, __float_as_uint(my_sum), my_max, 0u);
+        if (lane < cnt) p.rows[bt.row] = make_uint4(my_cnt, __float_as_uint(my_sum), my_max, 0u);
         wave_lds_sync();  // the next batch overwrites the staged records
     }
 }
 
-void launch_contrib_walk(hipStream_t s, const ContribWalkParams &p0) {
-    if (p0.num_tiles <= 0) return;
-    ContribWalkParams p = p0;
-    p.strip_exact = tuning("strip_exact", 1);
-    const dim3 grid((uint32_t)p.num_tiles), block(64);
-    if (tuning("guard", 0)) contrib_walk_kernel<true><<<grid, block, 0, s>>>(p);  // as the colour forward ran
-    else contrib_walk_kernel<false><<<grid, block, 0, s>>>(p);
+void launch_contrib_walk(hipStream_t s, const ContribWalkParams &p) {
+    if (p.src.num_tiles <= 0) return;
+    replay_launch(s, dim3((uint32_t)p.src.num_tiles), p, contrib_walk_kernel<false>, contrib_walk_kernel<true>);
 }
 
 // ------------------------------------------------------------------------------------------------

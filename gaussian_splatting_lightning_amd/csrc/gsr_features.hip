@@ -2,11 +2,11 @@
 // render's weights w_i(pix) = alpha_i T_i into out_features (C,H,W), and their backward.
 //
 // Kernels of their own beside render_fwd_v6_kernel / render_bwd_v5_kernel (both at their register budgets), so a call
-// without features launches exactly what it launched before.  All three read only what the colour forward recorded
-// (point_list, ranges, n_contrib, final_T, tile_last / tile_loaded, the 48-B render records) and evaluate alpha with the
-// composite's staged-record arithmetic (stage_rec_a/b, power2_at, v_exp_f32, min(0.99, o G), the power > 0 and
-// alpha < 1/255 skips, and under the "guard" knob its guarded decision), so the decisions and the weights are those of
-// the colour forward.
+// without features launches exactly what it launched before.  The two walks read only what the colour forward recorded
+// (ReplaySrc, and final_T) and are built from the replay pieces of gsr_replay.h -- tile prologue, pixel setup, batch
+// head, and the pair's alpha and pass decision in the composite's staged-record arithmetic (under the "guard" knob its
+// guarded decision) -- so the decisions and the weights are those of the colour forward.  Theirs here: the feature
+// rows in LDS, the accumulators, the wave reduction, the zero fill of the feature rows and the stores.
 //
 // Channel blocks: a launch carries FB = 8 (C <= 8) or 16 channels of the C; the walk is repeated per block.  The
 // forward's blocks are independent (grid.y); the backward's run one launch after the other, because each ADDS its
@@ -14,7 +14,7 @@
 // Gaussian's channels onto the pixel's upstream gradient enters dL/dalpha, the scalar "behind" accumulator follows
 // D <- D + alpha (g - D) from 0 (no background term), and both are linear in dL/dF, so a block's six moment sums are
 // formed with its own D and added.  One wave owns a tile's rows: a plain read-add-store, no atomics.
-#include "gsr_replay.h"  // FEAT_BATCH, feat_stage, feat_alpha_pass: shared with gsr_contrib.hip
+#include "gsr_replay.h"
 
 namespace gsr {
 
@@ -30,6 +30,15 @@ __device__ __forceinline__ void feat_load_rows(const float *__restrict__ feature
         s_f[j][c] = c0 + c < C ? features[(size_t)s_gid[j] * C + (c0 + c)] : 0.f;
     }
 }
+// One staged row back into registers (16-B LDS reads)
+template <int FB>
+__device__ __forceinline__ void feat_row(const float *row, float (&f)[FB]) {
+#pragma unroll
+    for (int c = 0; c < FB; c += 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(row + c);
+        f[c] = v.x, f[c + 1] = v.y, f[c + 2] = v.z, f[c + 3] = v.w;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // Feature forward (replay): one wave per (tile, channel block), 4 pixels per lane as the composite.  Walks
@@ -39,98 +48,61 @@ __device__ __forceinline__ void feat_load_rows(const float *__restrict__ feature
 // ------------------------------------------------------------------------------------------------
 template <int FB, bool GUARD = false>
 __global__ __launch_bounds__(64) void feat_fwd_kernel(FeatFwdParams p) {
-    __shared__ FwdRec s_rec[FEAT_BATCH];
-    __shared__ uint32_t s_gid[FEAT_BATCH];
-    __shared__ __attribute__((aligned(16))) float s_f[FEAT_BATCH][FB];
-    const int lane = threadIdx.x;
-    const int tile = blockIdx.x, c0 = (int)blockIdx.y * FB;
-    const int tx = tile % p.gx, ty = tile / p.gx;
-    const int px = tx * BLOCK_X + (lane & 15);
-    const int py0 = ty * BLOCK_Y + (lane >> 4);
-    const float pfx = (float)px;
-    const float row0 = (float)(ty * BLOCK_Y), col0 = (float)(tx * BLOCK_X);
-    const uint32_t r0 = __builtin_amdgcn_readfirstlane(p.ranges[tile].x);
-    const uint32_t tl = __builtin_amdgcn_readfirstlane(p.tile_last[tile]);
-    float T[PIX_PER_LANE], prow[PIX_PER_LANE], F[PIX_PER_LANE][FB];
-    uint32_t lastc[PIX_PER_LANE];
+    __shared__ FwdRec s_rec[REPLAY_BATCH];
+    __shared__ uint32_t s_gid[REPLAY_BATCH];
+    __shared__ __attribute__((aligned(16))) float s_f[REPLAY_BATCH][FB];
+    const int lane = threadIdx.x, c0 = (int)blockIdx.y * FB;
+    const ReplayTile t = replay_tile(p.src, (int)blockIdx.x, lane);
+    ReplayPixel q[PIX_PER_LANE];
+    float T[PIX_PER_LANE], F[PIX_PER_LANE][FB];
 #pragma unroll
     for (int k = 0; k < PIX_PER_LANE; k++) {
-        const int py = py0 + 4 * k;
-        const bool inside = px < p.W && py < p.H;
-        lastc[k] = inside ? p.n_contrib[(size_t)py * p.W + px] : 0u;
+        q[k] = replay_pixel(p.src, t, k);
         T[k] = 1.0f;
-        prow[k] = (float)py;
 #pragma unroll
         for (int c = 0; c < FB; c++) F[k][c] = 0.f;
     }
-    for (uint32_t b0 = 0; b0 < tl; b0 += FEAT_BATCH) {
-        const int cnt = (int)min((uint32_t)FEAT_BATCH, tl - b0);
-        float4 ra, rb;
-        const uint32_t my_m = feat_stage(p.rec, p.point_list, r0 + b0 + (uint32_t)lane, lane < cnt, lane, s_rec, s_gid,
-                                         p.strip_exact != 0, row0, col0, ra, rb);
-        uint64_t sk[PIX_PER_LANE], un = 0;
-#pragma unroll
-        for (int k = 0; k < PIX_PER_LANE; k++) {
-            sk[k] = __ballot((my_m >> k) & 1u);
-            un |= sk[k];
-        }
-        wave_lds_sync();
+    for (uint32_t b0 = 0; b0 < t.tl; b0 += REPLAY_BATCH) {
+        const int cnt = (int)min((uint32_t)REPLAY_BATCH, t.tl - b0);
+        ReplayBatch bt = replay_batch(p.src, t, t.r0 + b0, +1, cnt, lane, s_rec, s_gid);
         feat_load_rows<FB>(p.features, p.C, c0, cnt, lane, s_gid, s_f);
         wave_lds_sync();
-        while (un) {  // the instances that reach a strip, front to back
-            const int j = (int)__builtin_ctzll(un);
-            un &= ~(1ull << j);
-            const uint32_t idx = b0 + (uint32_t)j;
-            const float4 a = s_rec[j].a, b = s_rec[j].b;  // a: x, y, A, B; b: C, o, -, -
+        while (bt.un) {  // the instances that reach a strip, front to back
+            const int j = (int)__builtin_ctzll(bt.un);
+            bt.un &= ~(1ull << j);
+            const ReplayInst in = replay_inst(s_rec, s_gid, j, t.pfx);
             float f[FB];
-#pragma unroll
-            for (int c = 0; c < FB; c += 4) {
-                const float4 v = *reinterpret_cast<const float4 *>(&s_f[j][c]);
-                f[c] = v.x, f[c + 1] = v.y, f[c + 2] = v.z, f[c + 3] = v.w;
-            }
-            const float dx = a.x - pfx;
-            const float P0 = (a.z * dx) * dx, L = a.w * dx;
+            feat_row<FB>(s_f[j], f);
 #pragma unroll
             for (int k = 0; k < PIX_PER_LANE; k++) {
-                if (!((sk[k] >> j) & 1u)) continue;  // wave-uniform
-                const float power2 = power2_at(b.x, a.y - prow[k], P0, L);
-                const float alpha = fminf(0.99f, b.y * __builtin_amdgcn_exp2f(power2));
-                if (idx < lastc[k] && feat_alpha_pass<GUARD>(power2, alpha, p.rec, s_gid[j], pfx, prow[k])) {
-                    const float wgt = alpha * T[k];
+                if (!((bt.sk[k] >> j) & 1u)) continue;  // wave-uniform
+                const ReplayPair pr = replay_pair<GUARD>(p.src, in, b0 + (uint32_t)j, q[k], t.pfx);
+                if (pr.pass) {
+                    const float wgt = pr.alpha * T[k];
 #pragma unroll
                     for (int c = 0; c < FB; c++) F[k][c] = fmaf(f[c], wgt, F[k][c]);
-                    T[k] = T[k] * (1 - alpha);
+                    T[k] = T[k] * (1 - pr.alpha);
                 }
             }
         }
         wave_lds_sync();  // the next batch overwrites the staged records and rows
     }
-    const size_t HW = (size_t)p.W * p.H;
+    const size_t HW = (size_t)p.src.W * p.src.H;
 #pragma unroll
     for (int k = 0; k < PIX_PER_LANE; k++) {
-        const int py = py0 + 4 * k;
-        if (px < p.W && py < p.H) {
-            const size_t pid = (size_t)py * p.W + px;
+        const ReplayPixel e = replay_pixel(p.src, t, k);  // again: its index is not kept over the walk
 #pragma unroll
-            for (int c = 0; c < FB; c++)
-                if (c0 + c < p.C) p.out[(size_t)(c0 + c) * HW + pid] = F[k][c];
-        }
+        for (int c = 0; c < FB; c++)
+            if (e.inside && c0 + c < p.C) p.out[(size_t)(c0 + c) * HW + e.pid] = F[k][c];
     }
 }
 
-void launch_feat_fwd(hipStream_t s, const FeatFwdParams &p0) {
-    if (p0.num_tiles <= 0 || p0.C <= 0) return;
-    FeatFwdParams p = p0;
-    p.strip_exact = tuning("strip_exact", 1);
+void launch_feat_fwd(hipStream_t s, const FeatFwdParams &p) {
+    if (p.src.num_tiles <= 0 || p.C <= 0) return;
     const int fb = feat_block(p.C);
-    const dim3 grid((uint32_t)p.num_tiles, (uint32_t)div_up((uint32_t)p.C, (uint32_t)fb)), block(64);
-    if (tuning("guard", 0)) {  // the colour forward ran with the guard: the same decisions
-        if (fb == 8) feat_fwd_kernel<8, true><<<grid, block, 0, s>>>(p);
-        else feat_fwd_kernel<16, true><<<grid, block, 0, s>>>(p);
-        return;
-    }
-    if (fb == 8) feat_fwd_kernel<8><<<grid, block, 0, s>>>(p);
-    else feat_fwd_kernel<16><<<grid, block, 0, s>>>(p);
+    const dim3 grid((uint32_t)p.src.num_tiles, (uint32_t)div_up((uint32_t)p.C, (uint32_t)fb));
+    if (fb == 8) replay_launch(s, grid, p, feat_fwd_kernel<8, false>, feat_fwd_kernel<8, true>);
+    else replay_launch(s, grid, p, feat_fwd_kernel<16, false>, feat_fwd_kernel<16, true>);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -188,57 +160,36 @@ __device__ __forceinline__ void wave_reduce_store(const float *v, float *__restr
 template <int FB, bool GUARD = false>
 __global__ __launch_bounds__(64) void feat_bwd_kernel(FeatBwdParams p) {
     constexpr int NV = FB + 6 <= 16 ? 16 : 32;
-    __shared__ FwdRec s_rec[FEAT_BATCH];
-    __shared__ uint32_t s_gid[FEAT_BATCH];
-    __shared__ uint32_t s_row[FEAT_BATCH];
-    __shared__ __attribute__((aligned(16))) float s_f[FEAT_BATCH][FB];
-    __shared__ __attribute__((aligned(16))) float s_red[FEAT_BATCH][NV];
-    const int lane = threadIdx.x;
-    const int tile = blockIdx.x, c0 = p.c0;
-    const int tx = tile % p.gx, ty = tile / p.gx;
-    const int px = tx * BLOCK_X + (lane & 15);
-    const int py0 = ty * BLOCK_Y + (lane >> 4);
-    const float pfx = (float)px;
-    const float row0 = (float)(ty * BLOCK_Y), col0 = (float)(tx * BLOCK_X);
-    const uint32_t r0 = __builtin_amdgcn_readfirstlane(p.ranges[tile].x);
-    const uint32_t tl = __builtin_amdgcn_readfirstlane(p.tile_last[tile]);
-    const uint32_t loaded = __builtin_amdgcn_readfirstlane(p.tile_loaded[tile]);
+    __shared__ FwdRec s_rec[REPLAY_BATCH];
+    __shared__ uint32_t s_gid[REPLAY_BATCH];
+    __shared__ uint32_t s_row[REPLAY_BATCH];
+    __shared__ __attribute__((aligned(16))) float s_f[REPLAY_BATCH][FB];
+    __shared__ __attribute__((aligned(16))) float s_red[REPLAY_BATCH][NV];
+    const int lane = threadIdx.x, c0 = p.c0;
+    const ReplayTile t = replay_tile(p.src, (int)blockIdx.x, lane);
     // the instances the forward loaded but no pixel reached: zero feature rows (render_bwd zeroed their 40-B rows)
-    for (uint32_t e = (uint32_t)lane; e < (loaded > tl ? loaded - tl : 0u) * FB; e += 64)
-        p.frows[(size_t)p.sorted_u[r0 + tl + e / FB] * FB + e % FB] = 0.f;
-    if (tl == 0) return;
+    for (uint32_t e = (uint32_t)lane; e < (t.loaded > t.tl ? t.loaded - t.tl : 0u) * FB; e += 64)
+        p.frows[(size_t)p.src.sorted_u[t.r0 + t.tl + e / FB] * FB + e % FB] = 0.f;
+    if (t.tl == 0) return;
 
-    const size_t HW = (size_t)p.W * p.H;
-    float T[PIX_PER_LANE], D[PIX_PER_LANE], prow[PIX_PER_LANE], dF[PIX_PER_LANE][FB];
-    uint32_t lastc[PIX_PER_LANE];
+    const size_t HW = (size_t)p.src.W * p.src.H;
+    ReplayPixel q[PIX_PER_LANE];
+    float T[PIX_PER_LANE], D[PIX_PER_LANE], dF[PIX_PER_LANE][FB];
 #pragma unroll
     for (int k = 0; k < PIX_PER_LANE; k++) {
-        const int py = py0 + 4 * k;
-        const bool inside = px < p.W && py < p.H;
-        const size_t pid = inside ? (size_t)py * p.W + px : 0;
-        T[k] = inside ? p.final_T[pid] : 0.f;
-        lastc[k] = inside ? p.n_contrib[pid] : 0u;
+        q[k] = replay_pixel(p.src, t, k);
+        T[k] = q[k].inside ? p.final_T[q[k].pid] : 0.f;
         D[k] = 0.f;
-        prow[k] = (float)py;
 #pragma unroll
-        for (int c = 0; c < FB; c++) dF[k][c] = (inside && c0 + c < p.C) ? p.dL_dF[(size_t)(c0 + c) * HW + pid] : 0.f;
+        for (int c = 0; c < FB; c++)
+            dF[k][c] = (q[k].inside && c0 + c < p.C) ? p.dL_dF[(size_t)(c0 + c) * HW + q[k].pid] : 0.f;
     }
-    const float hW = 0.5f * p.W, hH = 0.5f * p.H;
+    const float hW = 0.5f * p.src.W, hH = 0.5f * p.src.H;
 
-    for (int bend = (int)tl; bend > 0; bend -= FEAT_BATCH) {
-        const int cnt = min(FEAT_BATCH, bend);
-        float4 my_a = make_float4(0, 0, 0, 0), my_b = my_a;
-        const uint32_t s_me = r0 + (uint32_t)(bend - 1 - lane);
-        const uint32_t my_m = feat_stage(p.rec, p.point_list, s_me, lane < cnt, lane, s_rec, s_gid, p.strip_exact != 0,
-                                         row0, col0, my_a, my_b);
-        if (lane < cnt) s_row[lane] = p.sorted_u[s_me];
-        uint64_t sk[PIX_PER_LANE], un = 0;
-#pragma unroll
-        for (int k = 0; k < PIX_PER_LANE; k++) {
-            sk[k] = __ballot((my_m >> k) & 1u);
-            un |= sk[k];
-        }
-        wave_lds_sync();
+    for (int bend = (int)t.tl; bend > 0; bend -= REPLAY_BATCH) {
+        const int cnt = min(REPLAY_BATCH, bend);
+        const ReplayBatch bt = replay_batch(p.src, t, t.r0 + (uint32_t)(bend - 1), -1, cnt, lane, s_rec, s_gid);
+        if (lane < cnt) s_row[lane] = bt.row;
         feat_load_rows<FB>(p.features, p.C, c0, cnt, lane, s_gid, s_f);
         wave_lds_sync();
         for (int j = 0; j < cnt; j++) {
@@ -246,29 +197,19 @@ __global__ __launch_bounds__(64) void feat_bwd_kernel(FeatBwdParams p) {
             float m[NV];
 #pragma unroll
             for (int v = 0; v < NV; v++) m[v] = 0.f;
-            if ((un >> j) & 1ull) {  // wave-uniform: the instance reaches a strip
-                const uint32_t idx = (uint32_t)(bend - 1 - j);
-                const float4 a = s_rec[j].a, b = s_rec[j].b;  // a: x, y, A, B; b: C, o, -, -
+            if ((bt.un >> j) & 1ull) {  // wave-uniform: the instance reaches a strip
+                const ReplayInst in = replay_inst(s_rec, s_gid, j, t.pfx);
                 float f[FB];
-#pragma unroll
-                for (int c = 0; c < FB; c += 4) {
-                    const float4 v = *reinterpret_cast<const float4 *>(&s_f[j][c]);
-                    f[c] = v.x, f[c + 1] = v.y, f[c + 2] = v.z, f[c + 3] = v.w;
-                }
-                const float dx = a.x - pfx;
-                const float P0 = (a.z * dx) * dx, L = a.w * dx;
+                feat_row<FB>(s_f[j], f);
                 float Q0 = 0.f, Q1 = 0.f, Q2 = 0.f;
 #pragma unroll
                 for (int k = 0; k < PIX_PER_LANE; k++) {
-                    if (!((sk[k] >> j) & 1u)) continue;  // wave-uniform
-                    const float dy = a.y - prow[k];
-                    const float power2 = power2_at(b.x, dy, P0, L);
-                    const float G = __builtin_amdgcn_exp2f(power2);
-                    const float alpha = fminf(0.99f, b.y * G);
-                    if (idx < lastc[k] && feat_alpha_pass<GUARD>(power2, alpha, p.rec, s_gid[j], pfx, prow[k])) {
+                    if (!((bt.sk[k] >> j) & 1u)) continue;  // wave-uniform
+                    const ReplayPair pr = replay_pair<GUARD>(p.src, in, (uint32_t)(bend - 1 - j), q[k], t.pfx);
+                    if (pr.pass) {
                         any = true;
-                        T[k] = T[k] * fast_rcp(1.f - alpha);
-                        const float wgt = alpha * T[k];
+                        T[k] = T[k] * fast_rcp(1.f - pr.alpha);
+                        const float wgt = pr.alpha * T[k];
                         float g = 0.f;
 #pragma unroll
                         for (int c = 0; c < FB; c++) {
@@ -276,20 +217,20 @@ __global__ __launch_bounds__(64) void feat_bwd_kernel(FeatBwdParams p) {
                             m[6 + c] = fmaf(wgt, dF[k][c], m[6 + c]);
                         }
                         const float d = g - D[k];
-                        D[k] = fmaf(alpha, d, D[k]);
-                        const float q = G * (d * T[k]);
-                        const float qdy = q * dy;
+                        D[k] = fmaf(pr.alpha, d, D[k]);
+                        const float q = pr.G * (d * T[k]);
+                        const float qdy = q * pr.dy;
                         Q0 += q;
                         Q1 += qdy;
-                        Q2 = fmaf(qdy, dy, Q2);
+                        Q2 = fmaf(qdy, pr.dy, Q2);
                     }
                 }
                 // the six moments in gradient-row order (S, Sx, Sy, Sxx, Sxy, Syy): dx is the lane's own
                 m[0] = Q0;
-                m[1] = Q0 * dx;
+                m[1] = Q0 * in.dx;
                 m[2] = Q1;
-                m[3] = m[1] * dx;
-                m[4] = Q1 * dx;
+                m[3] = m[1] * in.dx;
+                m[4] = Q1 * in.dx;
                 m[5] = Q2;
             }
             if (__ballot(any)) wave_reduce_store<NV>(m, s_red[j], lane);
@@ -300,10 +241,12 @@ __global__ __launch_bounds__(64) void feat_bwd_kernel(FeatBwdParams p) {
         if (lane < cnt) {
             const float *u = s_red[lane];
             const float S = u[0], Sx = u[1], Sy = u[2], Sxx = u[3], Sxy = u[4], Syy = u[5];
-            const float o = my_b.y, ca = my_a.z, cb = my_a.w, cc = my_b.x;  // the raw record's opacity and conic
+            const float o = bt.raw_b.y, ca = bt.raw_a.z, cb = bt.raw_a.w, cc = bt.raw_b.x;  // the raw opacity and conic
             float add[6];
-            add[0] = -o * hW * (ca * Sx + cb * Sy);
-            add[1] = -o * hH * (cb * Sx + cc * Sy);
+            // the fused product spelled out: the compiler's pick followed the registers' layout.  The other a*b + c*d
+            // forms of the walks (power2_at, the moment sums) are its choice still: replay_path_bits.json's scenes check
+            add[0] = -o * hW * fmaf(cb, Sy, ca * Sx);
+            add[1] = -o * hH * fmaf(cb, Sx, cc * Sy);
             add[2] = -0.5f * o * Sxx;
             add[3] = -0.5f * o * Sxy;
             add[4] = -0.5f * o * Syy;
@@ -327,18 +270,11 @@ __global__ __launch_bounds__(64) void feat_bwd_kernel(FeatBwdParams p) {
     }
 }
 
-void launch_feat_bwd(hipStream_t s, const FeatBwdParams &p0) {
-    if (p0.num_tiles <= 0) return;
-    FeatBwdParams p = p0;
-    p.strip_exact = tuning("strip_exact", 1);
-    const dim3 grid((uint32_t)p.num_tiles), block(64);
-    if (tuning("guard", 0)) {  // as the forward ran
-        if (feat_block(p.C) == 8) feat_bwd_kernel<8, true><<<grid, block, 0, s>>>(p);
-        else feat_bwd_kernel<16, true><<<grid, block, 0, s>>>(p);
-        return;
-    }
-    if (feat_block(p.C) == 8) feat_bwd_kernel<8><<<grid, block, 0, s>>>(p);
-    else feat_bwd_kernel<16><<<grid, block, 0, s>>>(p);
+void launch_feat_bwd(hipStream_t s, const FeatBwdParams &p) {
+    if (p.src.num_tiles <= 0) return;
+    const dim3 grid((uint32_t)p.src.num_tiles);
+    if (feat_block(p.C) == 8) replay_launch(s, grid, p, feat_bwd_kernel<8, false>, feat_bwd_kernel<8, true>);
+    else replay_launch(s, grid, p, feat_bwd_kernel<16, false>, feat_bwd_kernel<16, true>);
 }
 
 // ------------------------------------------------------------------------------------------------

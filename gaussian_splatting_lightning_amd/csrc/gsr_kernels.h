@@ -28,8 +28,6 @@ void launch_exclusive_scan_lookback(hipStream_t s, const uint32_t *in, const uin
 // keys0 (optional): read the first pass's keys from there instead of sc.k[0] (left unmodified).
 // gather (optional): the last pass also writes dst[i] = src[sorted value i] for each non-null pair; returns
 // whether it did (always, with a gather).
-// onesweep_ran (optional): set to whether the onesweep path ran, i.e. whether sc.ctrl[RS_CTRL_ERR] was cleared and
-// holds this sort's look-back error flag (the multi-kernel path never touches sc.ctrl).
 struct SortGather {
     const uint32_t *src = nullptr;
     uint32_t *dst = nullptr;
@@ -37,8 +35,7 @@ struct SortGather {
     uint4 *dst4 = nullptr;
 };
 bool launch_radix_sort(hipStream_t s, SortScratch &sc, uint32_t n, int nbits, bool keyed = false,
-                       const uint32_t *keys0 = nullptr, const SortGather *gather = nullptr,
-                       bool *onesweep_ran = nullptr);
+                       const uint32_t *keys0 = nullptr, const SortGather *gather = nullptr);
 // relative-key depth sort (multi-kernel path, up to 9-bit digits): see gsr_sort.hip
 void launch_depth_sort_rel(hipStream_t s, SortScratch &sc, uint32_t n, const uint32_t *keys0, uint32_t kbase,
                            uint32_t kcap, int bits, const SortGather *gather);
@@ -298,32 +295,37 @@ void launch_abs_gather(hipStream_t s, const AbsGatherParams &p);
 size_t camera_partials_bytes(int64_t n);
 void launch_camera_reduce(hipStream_t s, const PreprocessBwdParams &p, float *dview, float *dproj, float *dcampos);
 
+// What every replay of the colour forward reads of the state it recorded: filled once per call (gsr_api.hip) and
+// embedded in the param structs of the kernels that replay (the walk's shared pieces: gsr_replay.h)
+struct ReplaySrc {
+    int W, H, gx, gy, num_tiles;
+    const uint2 *ranges;
+    const uint32_t *point_list, *n_contrib, *tile_last, *tile_loaded;
+    const uint32_t *sorted_u;  // sorted position -> expansion index u: an instance's row is row u
+    const GRec *rec;
+    int strip_exact = 0;  // as RenderFwdParams::strip_exact (set by launch)
+};
+
 // ---- per-Gaussian feature channels (gsr_features.hip) ----
 constexpr int FEAT_MAX_C = 64;
 int feat_block(int C);  // channels one launch carries: 8 (C <= 8) or 16; the walks repeat per block
 // out (C,H,W) = sum_i alpha_i T_i features[i][c], the colour forward's weights replayed from its recorded state
 struct FeatFwdParams {
-    int W, H, gx, gy, num_tiles, C;
-    const uint2 *ranges;
-    const uint32_t *point_list, *n_contrib, *tile_last;
-    const GRec *rec;
+    ReplaySrc src;
+    int C;
     const float *features;  // (P,C), 4-B aligned
     float *out;
-    int strip_exact;  // as RenderFwdParams::strip_exact (set by launch)
 };
 void launch_feat_fwd(hipStream_t s, const FeatFwdParams &p);
 // One channel block [c0, c0 + feat_block(C)) of the feature compositing backward, after launch_render_bwd and before
 // launch_big_reduce: adds the block's geometry terms into rows[..][0..5] and writes frows (R x feat_block(C) floats by
 // expansion index: sum_pix w_i(pix) dL_dF_c(pix))
 struct FeatBwdParams {
-    int W, H, gx, gy, num_tiles, C, c0;
-    const uint2 *ranges;
-    const uint32_t *point_list, *n_contrib, *tile_last, *tile_loaded, *sorted_u;
-    const GRec *rec;
+    ReplaySrc src;
+    int C, c0;
     const float *final_T, *features, *dL_dF;  // dL_dF (C,H,W)
     float *rows, *frows;
     uint8_t *live;  // as RenderBwdParams::live, or null
-    int strip_exact;  // (set by launch)
 };
 void launch_feat_bwd(hipStream_t s, const FeatBwdParams &p);
 // out[g][c0 .. c0 + feat_block(C)) of dL_dfeatures (P,C): the Gaussian's frows summed in instance order under
@@ -345,13 +347,9 @@ void launch_feat_gather(hipStream_t s, const FeatGatherParams &p);
 // v = [m(pix) *] alpha_i T_i; per instance the wave's count, sum and max of v go to the instance's 16-B row
 // {count, sum bits, max bits, 0} by expansion index (zeros for a loaded instance no pixel takes).
 struct ContribWalkParams {
-    int W, H, gx, gy, num_tiles;
-    const uint2 *ranges;
-    const uint32_t *point_list, *n_contrib, *tile_last, *tile_loaded, *sorted_u;
-    const GRec *rec;
+    ReplaySrc src;
     const float *pixel_weights;  // (H,W) or null: a pixel whose weight is not > 0 is left out
     uint4 *rows;                 // R
-    int strip_exact;             // as RenderFwdParams::strip_exact (set by launch)
 };
 void launch_contrib_walk(hipStream_t s, const ContribWalkParams &p);
 // count / wsum / wmax (P each, any null) from the rows in instance order, by radius and inv only (the live flags belong
