@@ -149,7 +149,8 @@ EXPORTED_SYMBOLS = (
     "gsr_image_buffer_bytes", "gsr_bwd_scratch_bytes", "gsr_set_profiling", "gsr_num_stages", "gsr_stage_name",
     "gsr_stage_times", "gsr_reset_stage_times", "gsr_last_error", "gsr_build_info", "gsr_abi_version", "gsr_adam_sh_views_step",
     "gsr_stream_values_supported", "gsr_stream_signal", "gsr_stream_wait", "gsr_state_layout_query",
-    "gsr_set_tuning", "gsr_get_tuning", "gsr_ssim_num_partials", "gsr_ssim_forward", "gsr_ssim_backward", "gsr_adam_step", "gsr_sparse_adam_step",
+    "gsr_set_tuning", "gsr_get_tuning", "gsr_num_tunings", "gsr_tuning_name", "gsr_tuning_default",
+    "gsr_ssim_num_partials", "gsr_ssim_forward", "gsr_ssim_backward", "gsr_adam_step", "gsr_sparse_adam_step",
     "gsr_activations_forward", "gsr_activations_backward",
     "gsr_densify_workspace_bytes", "gsr_densify_classify", "gsr_densify_apply", "gsr_ply_unpack", "gsr_ply_pack",
     "gsr_knn_workspace_bytes", "gsr_knn_mean_dist2", "gsr_debug_wave_stamps",
@@ -284,6 +285,13 @@ def load(path: str | None = None):
     lib.gsr_state_layout_query.restype = None
     lib.gsr_set_tuning.argtypes = [ctypes.c_char_p, ctypes.c_int]
     lib.gsr_set_tuning.restype = None
+    if hasattr(lib, "gsr_num_tunings"):  # else a build loaded for A/Bs through GSR_LIB that stores any name unchecked
+        lib.gsr_set_tuning.restype = ctypes.c_int
+        lib.gsr_num_tunings.restype = ctypes.c_int
+        lib.gsr_tuning_name.argtypes = [ctypes.c_int]
+        lib.gsr_tuning_name.restype = ctypes.c_char_p
+        lib.gsr_tuning_default.argtypes = [ctypes.c_int]
+        lib.gsr_tuning_default.restype = ctypes.c_int
     if hasattr(lib, "gsr_get_tuning"):  # absent from pre-round-4 builds loaded for A/Bs through GSR_LIB
         lib.gsr_get_tuning.argtypes = [ctypes.c_char_p, ctypes.c_int]
         lib.gsr_get_tuning.restype = ctypes.c_int
@@ -295,11 +303,11 @@ def load(path: str | None = None):
         lib.gsr_abi_version.restype = ctypes.c_int
         if lib.gsr_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: C ABI version {lib.gsr_abi_version()}, this package needs {ABI_VERSION}")
-    _lib = lib
     # A/B experiments from the command line: GSR_TUNE="knob=value,knob=value" (gsr_set_tuning before first use)
     for kv in filter(None, os.environ.get("GSR_TUNE", "").split(",")):
         k, v = kv.split("=")
-        lib.gsr_set_tuning(k.strip().encode(), int(v))
+        _set_knob(lib, k.strip(), int(v))
+    _lib = lib
     return lib
 
 
@@ -381,21 +389,38 @@ def state_layout(P: int, R: int, W: int, H: int) -> dict:
             if getattr(StateLayout, name).offset + ctypes.sizeof(ctypes.c_size_t) <= filled}
 
 
+def _set_knob(lib, name: str, value: int) -> None:
+    if lib.gsr_set_tuning(name.encode(), int(value)):  # (None from a build that predates the knob table)
+        raise KeyError(lib.gsr_last_error().decode(errors="replace"))
+
+
+def tunings() -> dict:
+    """{knob: built-in default} of the loaded library ({} from a build that predates the knob table)."""
+    lib = load()
+    if not hasattr(lib, "gsr_num_tunings"):
+        return {}
+    return {lib.gsr_tuning_name(i).decode(): int(lib.gsr_tuning_default(i)) for i in range(lib.gsr_num_tunings())}
+
+
 def set_tuning(name: str, value: int) -> None:
-    """Internal A/B knob (see gsr_set_tuning)."""
-    load().gsr_set_tuning(name.encode(), int(value))
+    """Internal A/B knob (see gsr_set_tuning); KeyError for a name the library does not have."""
+    _set_knob(load(), name, value)
 
 
 TUNING_UNSET = -2 ** 31  # gsr_set_tuning(name, GSR_TUNING_UNSET): the knob's built-in default applies again
 
 
 def unset_tuning(name: str) -> None:
-    load().gsr_set_tuning(name.encode(), TUNING_UNSET)
+    _set_knob(load(), name, TUNING_UNSET)
 
 
 @contextlib.contextmanager
 def tuned(**knobs):
     """Set knobs for the body, then restore each one (its earlier value, or its built-in default if it was unset)."""
+    known = tunings()
+    for k in knobs:  # before anything is set
+        if known and k not in known:
+            raise KeyError(f"unknown knob \"{k}\"")
     before = {}
     for k in knobs:
         a, b = get_tuning(k, TUNING_UNSET), get_tuning(k, TUNING_UNSET + 1)

@@ -50,7 +50,8 @@ def _flags():
 def _needs_rebuild(obj: str, src: str) -> bool:
     if not os.path.exists(obj):
         return True
-    deps = [src] + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(INCLUDE, "gsrast.h")]
+    deps = [src] + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.def")) + \
+        [os.path.join(INCLUDE, "gsrast.h")]
     t = os.path.getmtime(obj)
     return any(os.path.getmtime(d) > t for d in deps)
 

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -24,16 +25,34 @@ using namespace gsr;
 
 namespace {
 
-std::mutex g_tune_mu;
-std::vector<std::pair<std::string, int>> g_tune;
+std::mutex g_tune_mu;  // stamp_buffer's
+
+// The knob table (gsr_knobs.def): names and built-in defaults, and per knob a value with its "set" flag.
+struct KnobInfo {
+    const char *name;
+    int def;
+};
+constexpr KnobInfo kKnobs[K_COUNT] = {
+#define GSR_KNOB(name, def, cls, doc) {#name, (def)},
+#include "gsr_knobs.def"
+#undef GSR_KNOB
+};
+std::atomic<int> g_knob_value[K_COUNT];
+std::atomic<bool> g_knob_set[K_COUNT];
+// read-only statistic, read through gsr_get_tuning: the last forward's depth-sort passes, 0 on the bucket path
+constexpr const char *kStatDepthPasses = "stat_depth_passes";
+std::atomic<int> g_stat_depth_passes{GSR_TUNING_UNSET};
+
+int find_knob(const char *name) {
+    for (int k = 0; name && k < K_COUNT; k++)
+        if (!strcmp(kKnobs[k].name, name)) return k;
+    return -1;
+}
 
 }  // namespace
 
-int gsr::tuning(const char *name, int default_value) {
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    for (auto &kv : g_tune)
-        if (kv.first == name) return kv.second;
-    return default_value;
+int gsr::tuning(Knob k) {
+    return g_knob_set[k].load(std::memory_order_relaxed) ? g_knob_value[k].load(std::memory_order_relaxed) : kKnobs[k].def;
 }
 
 uint4 *gsr::stamp_buffer(int which) {
@@ -145,9 +164,7 @@ struct StageScope {
     hipEvent_t a = nullptr;
     StageScope(hipStream_t s_, int st, bool dbg) : s(s_), stage(st), debug(dbg) {
         Profiler &p = prof();
-        // "prof_mask" (bit per Stage, default all): which stages get an event pair.  Every event adds a
-        // marker to the stream, so bench.py times its steps with events around the dominant kernel only.
-        if (p.enabled && ((tuning("prof_mask", -1) >> st) & 1)) {
+        if (p.enabled && ((tuning(K_prof_mask) >> st) & 1)) {
             std::lock_guard<std::mutex> lk(p.mu);
             a = p.get();
             if (a) (void)hipEventRecord(a, s);
@@ -651,14 +668,14 @@ static int fwd_bucket_plan(FwdCall &c) {
     const int P = c.P;
     BucketParams &bp = c.bp;
     bp.P = (uint32_t)P; bp.T = c.T; bp.gx = c.gx; bp.nbig = g.counters + CNT_BIG;
-    bp.nb = std::max(1u, std::min({(uint32_t)tuning("bk_blocks", 256), BK_MAX_BLOCKS, div_up(P, 1024)}));
+    bp.nb = std::max(1u, std::min({256u, BK_MAX_BLOCKS, div_up(P, 1024)}));  // 192 / 384 walk blocks measured slower (A.2)
     bp.gper = div_up(div_up(P, bp.nb), 256) * 256;  // whole preprocess blocks
     bp.nr = div_up(P, bp.gper);
     // extra walk blocks for the big rects (used only when the device's big-Gaussian count exceeds nr: bk_walk_blocks);
     // the block count is fixed here, before that count is read back.  2000 sparse-scene Gaussians at 1080p ran their
     // big rects on 2 blocks (count + scatter walks 220 + 310 us).  Only below half of that count of
     // range blocks: at cfg 3 (245 range blocks) 11 extra blocks measured +10 us of scatter (profiles/r4s_*)
-    const uint32_t big_blocks = std::min((uint32_t)tuning("bk_big_blocks", 256), BK_MAX_BLOCKS);
+    const uint32_t big_blocks = std::min((uint32_t)tuning(K_bk_big_blocks), BK_MAX_BLOCKS);
     bp.nb = 2 * bp.nr < big_blocks ? big_blocks : bp.nr;
     bp.tiles = g.tiles; bp.inst_start = g.inst_start; bp.block_sums = g.block_sums; bp.depth_key = g.depth_key;
     bp.big_list = g.big_list; bp.exp_rec = g.exp_rec;
@@ -668,8 +685,8 @@ static int fwd_bucket_plan(FwdCall &c) {
     bp.lpt_bcnt = im.lpt_bcnt;
     bp.ticket = g.counters + CNT_COL_TICKET; bp.tile_status = g.tile_status; bp.err = g.counters + CNT_OVERFLOW;
     bp.long_list = im.bk_long_list; bp.long_cnt = g.counters + CNT_LONG;
-    bp.lb_patience = (uint32_t)tuning("lb_patience", 1 << 16); bp.lb_force = tuning("lb_force", 0);
-    bp.xcd_major = tuning("bk_xcd", 1);
+    bp.lb_patience = LB_PATIENCE; bp.lb_force = tuning(K_lb_force);
+    bp.xcd_major = tuning(K_bk_xcd);
     // every buffer the column pass clears must be wired (a null one would fault the GPU, not fail here)
     if (!bp.tile_last || !bp.tile_loaded || !bp.ranges || !bp.tile_start || !bp.hist_pre)
         return fail(GSR_ERR_ARG, "internal: bucket binning buffer not set");
@@ -702,7 +719,7 @@ static int fwd_preprocess(FwdCall &c) {
     pp.focal_y = H / (2.0f * a->tan_fovy);
     pp.scale_modifier = a->scale_modifier;
     pp.antialiasing = a->antialiasing;
-    pp.cull = tuning("cull", 1);
+    pp.cull = tuning(K_cull);
     pp.means3D = a->means3D; pp.opacities = a->opacities; pp.scales = a->scales; pp.rotations = a->rotations;
     pp.cov3D_precomp = a->cov3D_precomp; pp.colors_precomp = a->colors_precomp; pp.shs = a->shs;
     pp.view = a->viewmatrix; pp.proj = a->projmatrix; pp.campos = a->campos;
@@ -712,14 +729,14 @@ static int fwd_preprocess(FwdCall &c) {
     pp.block_sums = g.block_sums;
     // The instance total only needs the per-Gaussian tile counts, so it is read back right after the
     // preprocess: its last workgroup writes the counters into pinned host memory and then a sequence word the
-    // host polls ("rb_spin" 1, default; 0: a copy plus an event, one more kernel and a barrier on the stream).
+    // host polls (debug = 1: a copy plus an event, one more kernel and a barrier on the stream).
     c.hw = pinned_words(c.dev);
     c.rb_ev = readback_event(c.dev);
     if (!c.hw || !c.rb_ev) return fail(GSR_ERR_HIP, "pinned host buffer / event allocation failed");
-    c.rb_spin = tuning("rb_spin", 1) != 0 && !c.dbg;
+    c.rb_spin = !c.dbg;
     c.seq = next_readback_seq(c.dev);
     pp.host_words = c.rb_spin ? c.hw : nullptr;
-    pp.stamps = tuning("stamp", 0) ? stamp_buffer(3) : nullptr;
+    pp.stamps = tuning(K_stamp) ? stamp_buffer(3) : nullptr;
     pp.seq = c.seq;
     // armed before the launch: an error reported after it, by this stage or a later one, still waits for the kernel
     // (the driver's frame holds it until the call returns)
@@ -727,8 +744,7 @@ static int fwd_preprocess(FwdCall &c) {
     c.inflight->armed = c.rb_spin;
     // the kept depth keys' range, for the radix path's relative depth sort: only where that sort can run (multi-kernel
     // depth sorts, P above the onesweep limit); else the range words stay empty and the sort takes its 32-bit keys
-    const uint32_t os_max = (uint32_t)tuning("onesweep_max_n", 3 << 20);
-    pp.depth_range = (tuning("depth_rel", 1) && (uint32_t)P > os_max) ? 1 : 0;
+    pp.depth_range = (tuning(K_depth_rel) && (uint32_t)P > (uint32_t)tuning(K_onesweep_max_n)) ? 1 : 0;
     GSR_STAGE(ST_PREPROCESS, c.dbg, launch_preprocess(stream, pp));
     if (!c.rb_spin) {
         GSR_HIP(hipMemcpyAsync(c.hw, g.counters, CNT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -737,9 +753,9 @@ static int fwd_preprocess(FwdCall &c) {
     // The bucket path's count pass needs no total either: whenever the tile count admits that path it is queued
     // right behind the preprocess, so the GPU runs it while the host waits (its scratch is in the image buffer;
     // if the total then selects the radix path, its results are simply unused).
-    c.bk = tuning("bucket", 1);
+    c.bk = tuning(K_bucket);
     c.bk_possible = c.bk == 2 ? c.T <= BK_MAX_TILES : c.bk == 1 && c.T <= BK_MAX_TILES / 2;
-    c.lpt = tuning("lpt", 1);
+    c.lpt = tuning(K_lpt);
     if (c.bk_possible) {
         const int rc = fwd_bucket_plan(c);
         if (rc) return rc;
@@ -755,11 +771,11 @@ static int fwd_readback(FwdCall &c) {
     // (a Python callback from rasterizer.py) after the readback put ~40 us of host work between the preprocess and
     // the next launch, longer than the queued count passes cover; so with a total from an earlier call on this
     // thread and device (readback_hint, read here before the wait) the buffer is requested before the wait, 25 %
-    // larger, and only re-requested when the total exceeds it ("bin_prealloc" 0: always after the wait).
+    // larger, and only re-requested when the total exceeds it.
     c.bin = nullptr;
     c.bin_cap = -1;
     const int64_t r_hint = readback_hint(c.dev);
-    if (r_hint > 0 && tuning("bin_prealloc", 1)) {
+    if (r_hint > 0) {
         c.bin_cap = std::min<int64_t>(r_hint + r_hint / 4 + 4096, 0xffffffffLL);
         c.bin = c.alloc(c.alloc_ctx, GSR_BUF_BINNING, carve_binning(nullptr, c.bin_cap, c.T, c.b));
         if (!c.bin) return fail(GSR_ERR_ALLOC, "binning buffer allocation failed");
@@ -792,7 +808,7 @@ static int fwd_readback(FwdCall &c) {
     // takes 0.20 ms against the radix path's 0.30; at 5M / 4K stress (1240 per tile) 4.4 ms against 1.4.
     // Otherwise the radix path: depth sort, depth-ordered expansion, stable tile sort.
     c.bucket = c.bk_possible && (c.bk == 2 || (uint64_t)c.R <= (uint64_t)BK_MAX_MEAN * c.T);
-    if (c.bucket) gsr_set_tuning("stat_depth_passes", 0);
+    if (c.bucket) g_stat_depth_passes.store(0, std::memory_order_relaxed);
     return GSR_OK;
 }
 
@@ -808,14 +824,14 @@ static int fwd_depth_sort(FwdCall &c) {
     // profiles/r6t_libab_sort_gather_cfg5.txt)
     SortGather ga;
     ga.src = g.tiles; ga.dst = g.tiles_sorted;
-    // Relative depth keys ("depth_rel" 1) where the sort takes the multi-kernel path: the kept keys span
+    // Relative depth keys where the sort takes the multi-kernel path: the kept keys span
     // kmax - kmin, so rs_rel_key maps them onto [0, span] and the culled ones onto span + 1, and the sort runs
     // ceil(bits / 9) passes instead of 4 (cfg 5: 26 bits, 3 passes of 9 bits)
     int rel_bits = 32;
-    const uint32_t os_max = (uint32_t)tuning("onesweep_max_n", 3 << 20);
-    if (tuning("depth_rel", 1) && c.kmin <= c.kmax && (uint32_t)P > os_max && c.kmax - c.kmin < 0xfffffffeu)
+    if (tuning(K_depth_rel) && c.kmin <= c.kmax && (uint32_t)P > (uint32_t)tuning(K_onesweep_max_n) &&
+        c.kmax - c.kmin < 0xfffffffeu)
         rel_bits = 32 - __builtin_clz(c.kmax - c.kmin + 1);
-    gsr_set_tuning("stat_depth_passes", rel_bits <= 27 ? (rel_bits + 8) / 9 : 4);
+    g_stat_depth_passes.store(rel_bits <= 27 ? (rel_bits + 8) / 9 : 4, std::memory_order_relaxed);
     if (rel_bits <= 27)
         GSR_STAGE(ST_DEPTH_SORT, c.dbg,
                   launch_depth_sort_rel(stream, g.sort, (uint32_t)P, g.depth_key, c.kmin, c.kmax - c.kmin + 1, rel_bits,
@@ -858,27 +874,23 @@ static int fwd_bin_bucket(FwdCall &c) {
     BucketParams &bp = c.bp;
     bp.keys = b.bk_keys; bp.inst_gid = b.inst_gid; bp.inv = b.inv; bp.R = R;
     // region scatter: keys into 16-tile regions first (long runs per block), then a partition pass into the tile
-    // buckets (gsr_bin.hip bk_partition_kernel) -- "bk_region" 1 (default) above 4096 tiles (short runs: cfg 3 has
-    // ~2 keys per block and tile), 2 always, 0 never (at 800x800, 2500 tiles, the direct scatter's 12 us is
-    // already below the partition pass alone)
-    const int bkr = tuning("bk_region", 1);
+    // buckets (gsr_bin.hip bk_partition_kernel)
+    const int bkr = tuning(K_bk_region);
     // (the tile-in-region rides in u's top bits: R <= 2^28; the automatic choice also wants >= 256 keys per region
     // on average, so that a partition chunk rarely spans more regions than its LDS bins cover)
     const uint32_t nreg = div_up(T, BK_REGION);
     bp.keys_reg = ((bkr == 2 || (bkr == 1 && T > 4096 && R >= 256u * nreg)) && R <= (1u << BK_REG_SHIFT))
                       ? b.bk_keys2 : nullptr;
     bp.order = lpt ? im.order_fwd : nullptr;
-    // per-XCD LPT orders for the whole-tile composites ("xcd_lpt" 1, with the backward's bucket lists)
-    c.xcd_fwd = lpt && lpt_append_range(T) && tuning("lpt_append", 1) && tuning("xcd_lpt", 1) &&
+    // per-XCD LPT orders for the whole-tile composites (with the backward's bucket lists)
+    c.xcd_fwd = lpt && lpt_append_range(T) && tuning(K_xcd_lpt) &&
                 render_fwd_parts((int)T) == 1;
     bp.order_xcd = c.xcd_fwd ? im.order_xcd : nullptr;
-    bp.lpt_shift = tuning("lpt_shift", 3);
+    bp.lpt_shift = LPT_SHIFT;
     GSR_STAGE(ST_BK_SCATTER, c.dbg, launch_bucket_scatter(stream, bp));  // and the forward LPT order
     SegSortParams sp;
-    // the long tiles lead the LPT order only while SEG_CAP + 1 is a multiple of the bucket width
     sp.T = T; sp.ranges = im.ranges;
-    sp.tile_order = (lpt && (((SEG_CAP + 1) >> tuning("lpt_shift", 3)) << tuning("lpt_shift", 3)) == SEG_CAP + 1)
-                        ? im.order_fwd : nullptr;
+    sp.tile_order = lpt ? im.order_fwd : nullptr;  // the long tiles lead it (LPT_SHIFT)
     sp.keys = b.bk_keys; sp.keys2 = b.bk_keys2;
     sp.sorted_u = b.sorted_u; sp.long_list = im.bk_long_list; sp.long_cnt = g.counters + CNT_LONG;
     GSR_STAGE(ST_SEG_SORT, c.dbg, launch_seg_sort(stream, sp));
@@ -950,18 +962,18 @@ static int fwd_composite(FwdCall &c) {
     rp.bg_image = c.e.background_image; rp.out_alpha = c.e.out_alpha;
     rp.out_color = a->out_color; rp.out_invdepth = a->out_invdepth; rp.final_T = im.final_T;
     rp.n_contrib = im.n_contrib; rp.tile_last = im.tile_last;
-    // checkpoints for the segmented backward ("bwd_seg" 1, spacing "seg_k" instances: 32 or a multiple of 64) while the image
+    // checkpoints for the segmented backward (spacing seg_k instances: 32 or a multiple of 64) while the image
     // has few tiles; the forward records in ck_flag whether it wrote them, so the backward never reads stale ones
     rp.ck_flag = im.ck_flag;
     // the backward's LPT order from bucket lists the whole-tile waves append (no ordering launch in the backward)
     rp.lpt_valid = im.lpt_valid;
     rp.strip_mask = b.strip_mask; rp.smask_valid = im.smask_valid;
-    if (lpt_append_range(T) && lpt && tuning("lpt_append", 1)) {
+    if (lpt_append_range(T) && lpt) {
         rp.lpt_bcnt = im.lpt_bcnt; rp.lpt_blist = im.lpt_blist;
     }
-    if (T <= SEG_MAX_TILES && tuning("bwd_seg", 1)) {
+    if (T <= SEG_MAX_TILES && tuning(K_bwd_seg)) {
         rp.ckpt = b.ckpt; rp.ctot = im.ctot;
-        const int k = tuning("seg_k", 64);  // cfg 2: 32 / 64 / 128 -> render_bwd 0.106 / 0.107 / 0.129 ms, render_fwd 0.070 / 0.065 / 0.062
+        const int k = tuning(K_seg_k);
         rp.ck_k = k <= 32 ? 32u : (uint32_t)(k / 64) * 64u;
     }
     if (c.R > 0 && (!rp.point_list || !rp.inst_gid || !rp.sorted_u))
@@ -1171,7 +1183,7 @@ static int bwd_carve(BwdCall &c) {
         if (!scratch) return fail(GSR_ERR_ALLOC, "backward scratch allocation failed");
     }
     carve_bwd_scratch(scratch, c.R, c.nbig, abs, fb, c.sc);
-    c.src = gather_src(a->radii, c, true, tuning("bwd_live", 1) != 0);
+    c.src = gather_src(a->radii, c, true, tuning(K_bwd_live) != 0);
     return GSR_OK;
 }
 
@@ -1182,12 +1194,12 @@ static int bwd_composite(BwdCall &c) {
     RenderBwdParams rp;
     rp.W = a->W; rp.H = a->H; rp.gx = c.gx; rp.gy = c.gy; rp.num_tiles = (int)c.T; rp.num_rendered = c.R;
     rp.ranges = c.im.ranges; rp.point_list = c.b.point_list; rp.n_contrib = c.im.n_contrib;
-    const int lpt = tuning("lpt", 1);
+    const int lpt = tuning(K_lpt);
     // the backward's own order (by tile_last; reusing the forward's range-length order measured slower)
     const bool own_order = lpt != 0;
     // in lpt_append_range the forward's whole-tile waves filled the bucket lists (render_bwd falls back to the
     // identity order if that forward did not, *lpt_valid = 0: the order never changes a result)
-    const bool lists = own_order && lpt_append_range(c.T) && tuning("lpt_append", 1);
+    const bool lists = own_order && lpt_append_range(c.T);
     if (own_order && !lists)
         launch_tile_order(stream, c.im.ranges, c.im.tile_last, 1, (int)c.T, c.im.order_bwd, c.im.lpt_hist);
     rp.tile_order = lpt ? (own_order ? (lists ? nullptr : c.im.order_bwd) : c.im.order_fwd) : nullptr;
@@ -1205,11 +1217,11 @@ static int bwd_composite(BwdCall &c) {
     rp.live_valid = c.g.counters + CNT_LIVE_VALID;
     rp.sorted_u = c.b.sorted_u;
     rp.strip_mask = c.b.strip_mask; rp.smask_valid = c.im.smask_valid;
-    if (c.T <= SEG_MAX_TILES && tuning("bwd_seg", 1)) {  // segmented walk (from the forward's checkpoints, if any)
+    if (c.T <= SEG_MAX_TILES && tuning(K_bwd_seg)) {  // segmented walk (from the forward's checkpoints, if any)
         rp.ckpt = c.b.ckpt; rp.ctot = c.im.ctot; rp.ck_flag = c.im.ck_flag;
         rp.seg_list = c.b.seg_list; rp.seg_count = c.im.seg_count;
     }
-    const bool planned = a->stages == GSR_BWD_ALL && tuning("bwd_prezero", 1) &&
+    const bool planned = a->stages == GSR_BWD_ALL && tuning(K_bwd_prezero) &&
                          zero_fill_plan(a, c.ab.dL_dmeans2D_abs, c.g0, c.g1, rp);
     bool launched = false;
     GSR_STAGE(ST_RENDER_BWD, c.dbg, launched = launch_render_bwd(stream, rp));
@@ -1835,19 +1847,25 @@ int gsr_mark_visible(int P, const float *means3D, const float *viewmatrix, const
     return GSR_OK;
 }
 
-void gsr_set_tuning(const char *name, int value) {
-    if (!name) return;
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    for (size_t k = 0; k < g_tune.size(); k++)
-        if (g_tune[k].first == name) {
-            if (value == GSR_TUNING_UNSET) g_tune.erase(g_tune.begin() + (long)k);  // back to the built-in default
-            else g_tune[k].second = value;
-            return;
-        }
-    if (value != GSR_TUNING_UNSET) g_tune.emplace_back(name, value);
+int gsr_set_tuning(const char *name, int value) {
+    const int k = find_knob(name);
+    if (k < 0) return fail(GSR_ERR_ARG, std::string("gsr_set_tuning: unknown knob \"") + (name ? name : "(null)") + "\"");
+    if (value != GSR_TUNING_UNSET) g_knob_value[k].store(value, std::memory_order_relaxed);
+    g_knob_set[k].store(value != GSR_TUNING_UNSET, std::memory_order_relaxed);
+    return GSR_OK;
 }
 
-int gsr_get_tuning(const char *name, int default_value) { return name ? tuning(name, default_value) : default_value; }
+int gsr_get_tuning(const char *name, int default_value) {
+    const int k = find_knob(name);
+    int v = GSR_TUNING_UNSET;
+    if (k >= 0 && g_knob_set[k].load(std::memory_order_relaxed)) v = g_knob_value[k].load(std::memory_order_relaxed);
+    else if (name && !strcmp(name, kStatDepthPasses)) v = g_stat_depth_passes.load(std::memory_order_relaxed);
+    return v != GSR_TUNING_UNSET ? v : default_value;
+}
+
+int gsr_num_tunings(void) { return K_COUNT; }
+const char *gsr_tuning_name(int i) { return (i >= 0 && i < K_COUNT) ? kKnobs[i].name : ""; }
+int gsr_tuning_default(int i) { return (i >= 0 && i < K_COUNT) ? kKnobs[i].def : 0; }
 
 int gsr_debug_wave_stamps(int which, uint32_t *host_dst, int max_slots) {
     uint4 *b = stamp_buffer(which);

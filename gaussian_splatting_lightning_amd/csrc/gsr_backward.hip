@@ -750,10 +750,9 @@ static void launch_parts(dim3 grid, dim3 block, hipStream_t s, const RenderBwdPa
 bool launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
     if (p.num_tiles <= 0) return false;
     RenderBwdParams q = p;
-    q.strip_exact = tuning("strip_exact", 1);
-    q.stamps = tuning("stamp", 0) ? stamp_buffer(1) : nullptr;
-    // threshold guard band ("guard" 1, the forward's knob; the segmented and whole-tile walks, not the parts form)
-    const bool gd = tuning("guard", 0) != 0;
+    q.strip_exact = tuning(K_strip_exact);
+    q.stamps = tuning(K_stamp) ? stamp_buffer(1) : nullptr;
+    const bool gd = tuning(K_guard) != 0;  // the segmented and whole-tile walks, not the parts form
     if (p.seg_list && p.ck_flag && p.ckpt && p.ctot && p.seg_count && p.num_tiles <= (int)SEG_MAX_TILES) {
         // segmented walk (800x800, 2500 tiles: one wave per 128-instance segment against 4 part-waves per tile)
         seg_list_kernel<<<1, 1024, 0, s>>>(p.tile_order, p.tile_last, p.num_tiles, p.ck_flag, q.seg_list, q.seg_count);
@@ -764,11 +763,10 @@ bool launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
         else launch_v5<false, false, true>(grid, block, s, q);
         return true;
     }
-    // "bwd_parts" 1, 2 or 4; 0 (default): 4 or 2 while that many part-waves fit within bwd_part_slots
-    // (1024 SIMDs x 12: 800x800 (2500 tiles) takes 4 parts, 0.143 ms against 0.149 in 2 and 0.181 whole; 1080p
-    // (8160 tiles) whole tiles)
-    int parts = tuning("bwd_parts", 0);
-    const int slots = tuning("bwd_part_slots", 12288);
+    // 4 or 2 parts while that many part-waves fit within 1024 SIMDs x 12: 800x800 (2500 tiles) takes 4 parts, 0.143 ms
+    // against 0.149 in 2 and 0.181 whole; 1080p (8160 tiles) whole tiles
+    constexpr int slots = 12288;
+    int parts = tuning(K_bwd_parts);
     if (parts == 0) parts = p.num_tiles * 4 <= slots ? 4 : p.num_tiles * 2 <= slots ? 2 : 1;
     if (gd) parts = 1;
     if (parts == 2 || parts == 4) {
@@ -784,10 +782,7 @@ bool launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
     }
     // with the forward's bucket lists the slots run to xcd_slots(T) (per-XCD lists); the extra ones exit
     const dim3 grid(p.lpt_blist ? xcd_slots((uint32_t)p.num_tiles) : (uint32_t)p.num_tiles), block(64);
-    // "bwd_union" -1 (auto): pair only the instances that reach a strip when tiles are long (mean above 1024
-    // instances: cfg 5 render_bwd 0.93 -> 0.90 ms; at cfg 3's 517 the plain walk is faster, 0.305 vs 0.329 ms);
-    // 0 / 1 force it
-    const int un = tuning("bwd_union", -1);
+    const int un = tuning(K_bwd_union);
     const bool u = un < 0 ? p.num_rendered > (uint64_t)1024 * (uint64_t)p.num_tiles : un != 0;
     if (gd) {
         if (p.dL_dinvdepth && u) launch_v5<true, true, false, true>(grid, block, s, q);

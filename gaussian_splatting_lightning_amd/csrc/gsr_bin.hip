@@ -513,82 +513,8 @@ __global__ __launch_bounds__(PART_THREADS) void bk_partition_kernel(BucketParams
 // ------------------------------------------------------------------------------------------------
 // Merge levels with k < E are register-only networks (compile-time directions); from k = E on, the
 // direction (i & k) == 0 depends only on the lane (i = l E + r, r < E <= k), so each stage is one lane mask.
-// Output: sorted_u (the expansion index of every sorted position), or, with lds_out, the padded sorted keys
-// [0, 64 E) into LDS.
-template <int E>
-__device__ __forceinline__ void seg_sort_wave_impl(const unsigned long long *__restrict__ keys, uint32_t start,
-                                                   uint32_t n, uint32_t *__restrict__ sorted_u,
-                                                   unsigned long long *__restrict__ lds_out, int lane) {
-    constexpr int LOGE = (E >= 64) ? 6 : (E >= 32) ? 5 : (E >= 16) ? 4 : (E >= 8) ? 3 : (E >= 4) ? 2 : (E >= 2) ? 1 : 0;
-    unsigned long long x[E];
-    const uint32_t base = (uint32_t)lane * E;
-    // every lane loads (a clamped index past n): loads in a branch each wait for their data before the next
-    // is issued, E serial memory round trips per sort
-#pragma unroll
-    for (int r = 0; r < E; r++) x[r] = keys[start + min(base + r, n - 1)];
-#pragma unroll
-    for (int r = 0; r < E; r++) x[r] = (base + r < n) ? x[r] : ~0ull;
-#pragma unroll
-    for (int lk = 1; lk < LOGE; lk++) {
-#pragma unroll
-        for (int lj = lk - 1; lj >= 0; lj--) {
-#pragma unroll
-            for (int r = 0; r < E; r++) {
-                if (r & (1 << lj)) continue;
-                const bool asc = (r & (1 << lk)) == 0;
-                const unsigned long long a = x[r], c = x[r | (1 << lj)];
-                const bool sw = asc ? (a > c) : (a < c);
-                x[r] = sw ? c : a;
-                x[r | (1 << lj)] = sw ? a : c;
-            }
-        }
-    }
-    for (int lk = LOGE > 1 ? LOGE : 1; lk <= LOGE + 6; lk++) {
-        const bool asc = (base & (1u << lk)) == 0;
-        for (int lj = lk - 1; lj >= LOGE; lj--) {
-            const int lm = 1 << (lj - LOGE);
-            const bool take_min = asc == ((lane & lm) == 0);
-            const int addr = (lane ^ lm) << 2;
-            // the exchanges of a batch are issued back to back: one LDS round trip per batch, not per key
-            constexpr int B = E < 16 ? E : 16;
-#pragma unroll
-            for (int r0 = 0; r0 < E; r0 += B) {
-                uint32_t ylo[B], yhi[B];
-#pragma unroll
-                for (int r = 0; r < B; r++) {
-                    ylo[r] = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)(uint32_t)x[r0 + r]);
-                    yhi[r] = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)(uint32_t)(x[r0 + r] >> 32));
-                }
-#pragma unroll
-                for (int r = 0; r < B; r++) {
-                    const unsigned long long y = ((unsigned long long)yhi[r] << 32) | ylo[r];
-                    x[r0 + r] = (take_min == (x[r0 + r] < y)) ? x[r0 + r] : y;
-                }
-            }
-        }
-#pragma unroll
-        for (int lj = LOGE - 1; lj >= 0; lj--) {
-#pragma unroll
-            for (int r = 0; r < E; r++) {
-                if (r & (1 << lj)) continue;
-                const unsigned long long a = x[r], c = x[r | (1 << lj)];
-                const bool sw = (a > c) == asc;
-                x[r] = sw ? c : a;
-                x[r | (1 << lj)] = sw ? a : c;
-            }
-        }
-    }
-    if (lds_out) {
-#pragma unroll
-        for (int r = 0; r < E; r++) lds_out[base + r] = x[r];
-    } else {
-#pragma unroll
-        for (int r = 0; r < E; r++)
-            if (base + r < n) sorted_u[start + base + r] = (uint32_t)x[r];
-    }
-}
-
-// 32-bit form of the same network.  Within one sort the keys are ranked by a 32-bit proxy
+//
+// Within one sort the keys are ranked by a 32-bit proxy
 //   k32 = ((depth bits - min depth bits) >> sh) << IDXB | index,   IDXB = log2(64 E),
 // with sh chosen so the depth offsets fit 32 - IDXB bits: unique keys, compare-exchanges are v_min/v_max
 // pairs and lane exchanges one ds_bpermute (about 2.5x fewer VALU ops than 64-bit keys).  The proxy orders
@@ -611,8 +537,10 @@ __device__ __forceinline__ void seg_sort_wave32(const unsigned long long *__rest
     const uint32_t base = (uint32_t)lane * E;
     unsigned long long x64[E];
     uint32_t dmin = 0xffffffffu, dmax = 0u;
+    // every lane loads (a clamped index past n): loads in a branch each wait for their data before the next
+    // is issued, E serial memory round trips per sort
 #pragma unroll
-    for (int r = 0; r < E; r++) x64[r] = keys[start + min(base + r, n - 1)];  // unconditional loads (as above)
+    for (int r = 0; r < E; r++) x64[r] = keys[start + min(base + r, n - 1)];
 #pragma unroll
     for (int r = 0; r < E; r++) {
         const bool valid = base + r < n;
@@ -731,14 +659,10 @@ __device__ __forceinline__ void seg_sort_wave32(const unsigned long long *__rest
     }
 }
 
-// Wrappers.  P32: the proxy-key sort; P32 = false: the 64-bit network (knob "seg32" 0, the A/B reference).
-template <int E, bool P32>
+// Wrappers of the proxy-key sort.
+template <int E>
 __device__ __forceinline__ void seg_sort_wave(const unsigned long long *keys, uint32_t start, uint32_t n,
                                               uint32_t *sorted_u, int lane, unsigned long long *scratch) {
-    if (!P32) {
-        seg_sort_wave_impl<E>(keys, start, n, sorted_u, nullptr, lane);
-        return;
-    }
     unsigned long long y[E];
     seg_sort_wave32<E>(keys, start, n, scratch, lane, y);
     const uint32_t base = (uint32_t)lane * E;
@@ -747,13 +671,9 @@ __device__ __forceinline__ void seg_sort_wave(const unsigned long long *keys, ui
         if (base + r < n) sorted_u[start + base + r] = (uint32_t)y[r];
 }
 // sorted (padded) keys into lds_out, which is also the scratch
-template <int E, bool P32>
+template <int E>
 __device__ __forceinline__ void seg_sort_wave_to_lds(const unsigned long long *keys, uint32_t start, uint32_t n,
                                                      unsigned long long *lds_out, int lane) {
-    if (!P32) {
-        seg_sort_wave_impl<E>(keys, start, n, nullptr, lds_out, lane);
-        return;
-    }
     unsigned long long y[E];
     seg_sort_wave32<E>(keys, start, n, lds_out, lane, y);
     wave_lds_sync();  // every lane's gathers done before the scratch is overwritten
@@ -814,7 +734,6 @@ __device__ __forceinline__ void seg_merge_ranks(const unsigned long long *__rest
     }
 }
 
-template <bool P32>
 __device__ __forceinline__ void seg_lds_sort(const unsigned long long *__restrict__ keys, uint32_t start, uint32_t n,
                                              uint32_t *__restrict__ sorted_u, unsigned long long *__restrict__ keys_out,
                                              unsigned long long *__restrict__ s_x, int w, int lane,
@@ -822,7 +741,7 @@ __device__ __forceinline__ void seg_lds_sort(const unsigned long long *__restric
     const uint32_t nch = (n + SB_CHUNK - 1) / SB_CHUNK;
     for (uint32_t c = (uint32_t)w; c < nch; c += 4) {
         const uint32_t c0 = c * SB_CHUNK;
-        seg_sort_wave_to_lds<8, P32>(keys, start + c0, min(SB_CHUNK, n - c0), s_x + c0, lane);
+        seg_sort_wave_to_lds<8>(keys, start + c0, min(SB_CHUNK, n - c0), s_x + c0, lane);
     }
     __syncthreads();
     if (t_mid) *t_mid = stamp_now();
@@ -834,11 +753,10 @@ __device__ __forceinline__ void seg_lds_sort(const unsigned long long *__restric
 // A tile above SEG_BLOCK_CAP instances, by one workgroup: SEG_BLOCK_CAP-key chunks sorted in LDS and written to
 // keys2, then every key placed by its rank in each other chunk (binary searches over the workgroup's own stores,
 // ordered by a device-scope fence).
-template <bool P32>
 __device__ void seg_tile_chunked(const SegSortParams &p, uint2 rg, uint32_t n, unsigned long long *s_x, int w,
                                  int lane) {
     for (uint32_t c0 = 0; c0 < n; c0 += SEG_BLOCK_CAP)
-        seg_lds_sort<P32>(p.keys, rg.x + c0, min(SEG_BLOCK_CAP, n - c0), nullptr, p.keys2, s_x, w, lane);
+        seg_lds_sort(p.keys, rg.x + c0, min(SEG_BLOCK_CAP, n - c0), nullptr, p.keys2, s_x, w, lane);
     __threadfence();
     __syncthreads();
     const unsigned long long *kk = p.keys2 + rg.x;
@@ -863,16 +781,15 @@ __device__ void seg_tile_chunked(const SegSortParams &p, uint2 rg, uint32_t n, u
 }
 
 // Every tile, in one persistent launch (the workgroups loop over the tiles, whose counts are only known on the
-// device, so every wave reaches the exit), on 32-bit proxy keys (P32, else on the 64-bit keys: the A/B reference,
-// knob "seg32"):
+// device, so every wave reaches the exit), on 32-bit proxy keys:
 //   1. tiles above SEG_CAP instances, one workgroup each: up to SEG_BLOCK_CAP in LDS (seg_lds_sort), longer ones in
 //      chunks (seg_tile_chunked).  With the LPT order they are exactly its first long_cnt[0] + long_cnt[1] slots
 //      (SEG_CAP + 1 is a multiple of the LPT bucket width), taken longest first; without it, lists 0 and 1;
 //   2. then the short tiles, one wave each (seg_sort_wave), again longest first.
 // Proxy-key ties are repaired in place (seg_sort_wave32), so no second launch is needed (round 4 handed unresolved
 // tie tiles, and the tiles above SEG_BLOCK_CAP, to a seg_huge launch whose ~5-us floor every step paid).
-template <bool P32, int MIN_WAVES = 1>
-__global__ __launch_bounds__(256, MIN_WAVES) void seg_sort_kernel(SegSortParams p) {
+// 6 waves per SIMD (80 VGPRs): 0.053 vs 0.060 ms at 4 (profiles/r6ai_ab_launch_knobs_cfg3.txt)
+__global__ __launch_bounds__(256, 6) void seg_sort_kernel(SegSortParams p) {
     __shared__ unsigned long long s_x[SEG_BLOCK_CAP];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint32_t n0 = p.long_cnt[0], nlong = n0 + p.long_cnt[1];
@@ -882,12 +799,12 @@ __global__ __launch_bounds__(256, MIN_WAVES) void seg_sort_kernel(SegSortParams 
         const uint32_t n = rg.y - rg.x;
         if (n <= SEG_CAP) continue;  // workgroup-uniform
         if (n > SEG_BLOCK_CAP) {
-            seg_tile_chunked<P32>(p, rg, n, s_x, w, lane);
+            seg_tile_chunked(p, rg, n, s_x, w, lane);
             continue;
         }
         const uint32_t t0 = p.stamps ? stamp_now() : 0u;
         uint32_t t1 = 0;
-        seg_lds_sort<P32>(p.keys, rg.x, n, p.sorted_u, nullptr, s_x, w, lane, p.stamps ? &t1 : nullptr);
+        seg_lds_sort(p.keys, rg.x, n, p.sorted_u, nullptr, s_x, w, lane, p.stamps ? &t1 : nullptr);
         if (p.stamps && threadIdx.x == 0 && i < (uint32_t)STAMP_SLOTS) p.stamps[i] = make_uint4(t0, t1, stamp_now(), n);
     }
     const uint32_t s0 = p.tile_order ? nlong : 0u;
@@ -899,10 +816,10 @@ __global__ __launch_bounds__(256, MIN_WAVES) void seg_sort_kernel(SegSortParams 
         const uint32_t n = rg.y - rg.x;
         if (n == 0 || n > SEG_CAP) continue;  // wave-uniform
         unsigned long long *scratch = s_x + w * SB_WAVE_SCRATCH;
-        if (n <= 64u) seg_sort_wave<1, P32>(p.keys, rg.x, n, p.sorted_u, lane, scratch);
-        else if (n <= 128u) seg_sort_wave<2, P32>(p.keys, rg.x, n, p.sorted_u, lane, scratch);
-        else if (n <= 256u) seg_sort_wave<4, P32>(p.keys, rg.x, n, p.sorted_u, lane, scratch);
-        else seg_sort_wave<8, P32>(p.keys, rg.x, n, p.sorted_u, lane, scratch);
+        if (n <= 64u) seg_sort_wave<1>(p.keys, rg.x, n, p.sorted_u, lane, scratch);
+        else if (n <= 128u) seg_sort_wave<2>(p.keys, rg.x, n, p.sorted_u, lane, scratch);
+        else if (n <= 256u) seg_sort_wave<4>(p.keys, rg.x, n, p.sorted_u, lane, scratch);
+        else seg_sort_wave<8>(p.keys, rg.x, n, p.sorted_u, lane, scratch);
     }
 }
 
@@ -928,10 +845,8 @@ static void launch_walk(hipStream_t s, const BucketParams &p, uint32_t grid) {
 
 void launch_bucket_count(hipStream_t s, const BucketParams &p) {
     launch_walk<false>(s, p, p.nb);
-    // "bk_colt" 32 (default): 32 tiles per column workgroup, the lane halves splitting the rows; 64: one lane per tile
-    if (tuning("bk_colw", 16) >= 16 && tuning("bk_colt", 32) == 32) bk_columns_kernel<16, 32><<<div_up(p.T, 32), 1024, 0, s>>>(p);
-    else if (tuning("bk_colw", 16) >= 16) bk_columns_kernel<16><<<div_up(p.T, 64), 1024, 0, s>>>(p);
-    else bk_columns_kernel<4><<<div_up(p.T, 64), 256, 0, s>>>(p);
+    // 32 tiles per 16-wave column workgroup, the lane halves splitting the rows
+    bk_columns_kernel<16, 32><<<div_up(p.T, 32), 1024, 0, s>>>(p);
 }
 
 // plus one workgroup for the forward LPT order when p.order is set
@@ -945,16 +860,10 @@ void launch_bucket_scatter(hipStream_t s, const BucketParams &p) {
 void launch_seg_sort(hipStream_t s, const SegSortParams &p0) {
     if (p0.T == 0) return;
     SegSortParams p = p0;
-    p.stamps = tuning("stamp", 0) ? stamp_buffer(2) : nullptr;
+    p.stamps = tuning(K_stamp) ? stamp_buffer(2) : nullptr;
     // one wave per tile up to 16384 tiles (cfg 3, 8160 tiles: 2040 workgroups, seg_sort 0.0490 -> 0.0472 ms against a
     // 1536-workgroup cap, profiles/r6ai_ab_launch_knobs_cfg3.txt)
-    const uint32_t grid = std::min(div_up(p.T, 4), (uint32_t)tuning("seg_grid", 4096));
-    const int minw = tuning("seg_minw", 6);  // 80 VGPRs: 0.053 vs 0.060 ms at 4 waves/SIMD
-    if (tuning("seg32", 1) && minw >= 7) seg_sort_kernel<true, 7><<<grid, 256, 0, s>>>(p);
-    else if (tuning("seg32", 1) && minw == 6) seg_sort_kernel<true, 6><<<grid, 256, 0, s>>>(p);
-    else if (tuning("seg32", 1) && minw == 5) seg_sort_kernel<true, 5><<<grid, 256, 0, s>>>(p);
-    else if (tuning("seg32", 1)) seg_sort_kernel<true><<<grid, 256, 0, s>>>(p);
-    else seg_sort_kernel<false><<<grid, 256, 0, s>>>(p);
+    seg_sort_kernel<<<std::min(div_up(p.T, 4), 4096u), 256, 0, s>>>(p);
 }
 
 }  // namespace gsr

@@ -12,7 +12,15 @@
 
 namespace gsr {
 
-int tuning(const char *name, int default_value);  // gsr_api.hip: runtime knobs (gsr_set_tuning)
+// Runtime knobs (gsr_set_tuning; gsr_knobs.def is the list, with defaults and documentation): K_<name>.  The
+// defaults are the shipped configuration; a knob that is not set reads as its default.
+enum Knob : int {
+#define GSR_KNOB(name, def, cls, doc) K_##name,
+#include "gsr_knobs.def"
+#undef GSR_KNOB
+    K_COUNT
+};
+int tuning(Knob k);  // gsr_api.hip: two relaxed atomic loads
 
 constexpr int BLOCK_X = 16;
 constexpr int BLOCK_Y = 16;
@@ -100,6 +108,9 @@ constexpr uint32_t BK_REGION = 1u << GSR_BK_REGION_LOG2;  // tiles per region of
 constexpr int BK_REG_SHIFT = 32 - GSR_BK_REGION_LOG2;    // the region scatter carries a key's tile-in-region in u's top bits
 constexpr uint32_t SEG_CAP = 511;         // longest tile the per-wave register sort takes (8 keys per lane);
                                           // SEG_CAP + 1 is a multiple of the LPT bucket width (seg_block)
+constexpr int LPT_SHIFT = 3;  // narrowest LPT bucket: 2^3 instances (lpt_order_block's shift0)
+static_assert((SEG_CAP + 1) % (1u << LPT_SHIFT) == 0, "the long tiles must lead the LPT order (seg_sort_kernel)");
+constexpr uint32_t LB_PATIENCE = 1u << 16;  // look-back polls before recomputing an unpublished predecessor
 constexpr uint32_t SEG_BLOCK_CAP = 2048;  // longest tile one workgroup sorts (4 waves x 512 keys); longer: chunks
 
 // One Gaussian's render record: interleaved rather than three arrays, so the composite passes' random gathers
@@ -180,8 +191,8 @@ struct TileSortPlan {
 inline TileSortPlan tile_sort_plan(uint32_t num_tiles) {
     TileSortPlan t;
     const int bits = tile_key_bits(num_tiles);
-    t.k16 = num_tiles <= 65536u && tuning("tile_key16", 1) != 0;
-    t.digit_bits = t.k16 ? tuning("tile_db", 8) : 8;  // cfg 5: 8-bit digits 0.75 ms, 5-bit 1.03 (r4d)
+    t.k16 = num_tiles <= 65536u && tuning(K_tile_key16) != 0;
+    t.digit_bits = t.k16 ? tuning(K_tile_db) : 8;
     if (t.digit_bits < 4 || t.digit_bits > 8) t.digit_bits = 8;
     t.passes = (bits + t.digit_bits - 1) / t.digit_bits;
     return t;

@@ -611,13 +611,13 @@ __global__ __launch_bounds__(1024) void lpt_scatter_kernel(const uint2 *__restri
 void launch_tile_order(hipStream_t s, const uint2 *ranges, const uint32_t *tile_last, int use_last, int T,
                        uint32_t *order, uint32_t *scratch) {
     if (T <= 0) return;
-    if (scratch && T > tuning("lpt_multi_tiles", 4096)) {  // cfg 3 (8160 tiles): step -12 us against one workgroup (14 us)
+    if (scratch && T > 4096) {  // cfg 3 (8160 tiles): step -12 us against one workgroup (14 us)
         const uint32_t g = div_up((uint32_t)T, (uint32_t)LPT_WG_TILES);
         lpt_hist_kernel<<<g, 1024, 0, s>>>(ranges, tile_last, use_last, T, scratch);
         lpt_scatter_kernel<<<g, 1024, 0, s>>>(ranges, tile_last, use_last, T, scratch, order);
         return;
     }
-    tile_order_kernel<<<1, 1024, 0, s>>>(ranges, tile_last, use_last, T, tuning("lpt_shift", 3), order);
+    tile_order_kernel<<<1, 1024, 0, s>>>(ranges, tile_last, use_last, T, LPT_SHIFT, order);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -892,13 +892,13 @@ __global__ __launch_bounds__(256, MIN_WAVES) void render_fwd_v6_kernel(RenderFwd
     stamp_store(p.stamps, slot, t_start, lane);
 }
 
-// "fwd_parts" 1, 2 or 4; 0 (default): 4 when that many part-waves still fit the GPU's ~8 resident waves per SIMD,
-// twice over (small images, where one heavy tile's latency sets the kernel time), else whole tiles (measured at
-// 1080p, 8160 tiles: whole tiles 0.175 ms against 0.196 in 2 parts; at 800x800, 2500 tiles: 4 parts 0.073, 2 parts
-// 0.092, whole 0.126)
+// 4 parts when that many part-waves still fit the GPU's ~8 resident waves per SIMD, twice over (FWD_PART_SLOTS; small
+// images, where one heavy tile's latency sets the kernel time), else whole tiles (measured at 1080p, 8160 tiles: whole
+// tiles 0.175 ms against 0.196 in 2 parts; at 800x800, 2500 tiles: 4 parts 0.073, 2 parts 0.092, whole 0.126)
+constexpr int FWD_PART_SLOTS = 16384;
 int render_fwd_parts(int num_tiles) {
-    int parts = tuning("fwd_parts", 0);
-    if (parts == 0) parts = num_tiles * 4 <= tuning("fwd_part_slots", 16384) ? 4 : 1;
+    int parts = tuning(K_fwd_parts);
+    if (parts == 0) parts = num_tiles * 4 <= FWD_PART_SLOTS ? 4 : 1;
     return (parts == 2 || parts == 4) ? parts : 1;
 }
 
@@ -913,17 +913,15 @@ static void launch_fwd_form(dim3 grid, dim3 block, hipStream_t s, const RenderFw
 void launch_render_fwd(hipStream_t s, const RenderFwdParams &p0) {
     if (p0.num_tiles <= 0) return;
     RenderFwdParams p = p0;
-    p.strip_exact = tuning("strip_exact", 1);
-    p.stamps = tuning("stamp", 0) ? stamp_buffer(0) : nullptr;
+    p.strip_exact = tuning(K_strip_exact);
+    p.stamps = tuning(K_stamp) ? stamp_buffer(0) : nullptr;
     const int parts = render_fwd_parts(p.num_tiles);
     if (parts != 1) p.xcd = 0;
     const dim3 grid(div_up(p.xcd ? (uint64_t)xcd_slots((uint32_t)p.num_tiles) : (uint64_t)p.num_tiles * parts, 4)),
         block(256);
-    // threshold guard band ("guard" 1; the default launch shapes only, and the backward must run with the same knob)
-    // exact strip masks for the backward ("smask" 1): whole tiles only
-    const bool sm = parts == 1 && p.strip_mask && tuning("smask", 1);
+    const bool sm = parts == 1 && p.strip_mask && tuning(K_smask);  // whole tiles only
     if (!sm) p.strip_mask = nullptr;
-    if (tuning("guard", 0)) {  // 6 waves per SIMD whole-tile: the guard's double exp needs the registers
+    if (tuning(K_guard)) {  // the default launch shapes only; 6 waves per SIMD whole-tile: the guard's double exp needs the registers
         if (parts == 1 && sm) launch_fwd_form<4, 6, false, true, true>(grid, block, s, p);
         else if (parts == 1) launch_fwd_form<4, 6, false, true>(grid, block, s, p);
         else if (parts == 4 && p.ckpt && p.ctot && p.ck_k >= CK_MIN_K && p.ck_k % 32 == 0 &&
@@ -936,14 +934,14 @@ void launch_render_fwd(hipStream_t s, const RenderFwdParams &p0) {
     if (parts == 1) {
         // 8 waves per SIMD (64 VGPRs, one 8-byte spill outside the pair loop): cfg3 0.180 -> 0.172 ms, cfg5 0.517 ->
         // 0.478 ms against 6 waves (65 VGPRs, i.e. 7 resident)
-        const int mw = tuning("fwd_whole_waves", 8);
+        const int mw = tuning(K_fwd_whole_waves);
         if (sm) launch_fwd_form<4, 8, false, false, true>(grid, block, s, p);
         else if (mw >= 8) launch_fwd_form<4, 8>(grid, block, s, p);
         else if (mw >= 6) launch_fwd_form<4, 6>(grid, block, s, p);
         else launch_fwd_form<4, 4>(grid, block, s, p);
         return;
     }
-    const int mw = tuning("fwd_part_waves", 8);
+    const int mw = tuning(K_fwd_part_waves);
     if (parts == 4 && p.ckpt && p.ctot && p.ck_k >= CK_MIN_K && p.ck_k % 32 == 0 && (p.ck_k == 32 || p.ck_k % 64 == 0))
         launch_fwd_form<1, 8, true>(grid, block, s, p);
     else if (parts == 2 && mw >= 8) launch_fwd_form<2, 8>(grid, block, s, p);

@@ -676,9 +676,9 @@ template <bool CAM>
 static void launch_preprocess_bwd_t(hipStream_t s, const PreprocessBwdParams &p, const uint32_t grid) {
     // the joint row gather and the LDS-staged dL/dsh stores; without dL/dsh (the compact multi-view exchange) only
     // the gather, which the per-lane path pays ~40 % of the kernel for
-    if ((p.dL_dsh ? p.sh_vec16 : true) && tuning("pbwd_lds_sh", 1) && p.prezeroed)
+    if ((p.dL_dsh ? p.sh_vec16 : true) && tuning(K_pbwd_lds_sh) && p.prezeroed)
         preprocess_bwd_kernel<true, true, CAM><<<grid, 256, 0, s>>>(p);
-    else if ((p.dL_dsh ? p.sh_vec16 : true) && tuning("pbwd_lds_sh", 1))
+    else if ((p.dL_dsh ? p.sh_vec16 : true) && tuning(K_pbwd_lds_sh))
         preprocess_bwd_kernel<true, false, CAM><<<grid, 256, 0, s>>>(p);
     else
         preprocess_bwd_kernel<false, false, CAM><<<grid, 256, 0, s>>>(p);

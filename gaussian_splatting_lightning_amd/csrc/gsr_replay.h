@@ -132,8 +132,8 @@ __device__ __forceinline__ ReplayPair replay_pair(const ReplaySrc &s, const Repl
 template <typename Params>
 void replay_launch(hipStream_t s, dim3 grid, const Params &p0, void (*plain)(Params), void (*guarded)(Params)) {
     Params p = p0;
-    p.src.strip_exact = tuning("strip_exact", 1);
-    (tuning("guard", 0) ? guarded : plain)<<<grid, dim3(64), 0, s>>>(p);
+    p.src.strip_exact = tuning(K_strip_exact);
+    (tuning(K_guard) ? guarded : plain)<<<grid, dim3(64), 0, s>>>(p);
 }
 
 }  // namespace gsr

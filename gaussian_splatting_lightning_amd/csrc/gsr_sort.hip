@@ -108,9 +108,9 @@ __global__ __launch_bounds__(NT) void scan_lookback_kernel(const uint32_t *__res
 void launch_exclusive_scan_lookback(hipStream_t s, const uint32_t *in, const uint32_t *idx, uint32_t n, uint32_t *out,
                                     uint64_t *status, uint32_t *ticket, uint32_t *flags) {
     // status (div_up(n + 1, SCAN_TILE) words) and *ticket must be zero (cleared with the forward's counters)
-    const uint32_t pat = (uint32_t)tuning("lb_patience", 1 << 16);
-    const int force = tuning("lb_force", 0);
-    const int snt = tuning("scan_nt", 2048);  // 256: 256 x 16 per workgroup
+    const uint32_t pat = LB_PATIENCE;
+    const int force = tuning(K_lb_force);
+    const int snt = tuning(K_scan_nt);
     if (snt == 2048) {  // 1024 threads x 32 items
         const uint32_t nb8 = div_up(n + 1, (uint32_t)(8 * SCAN_TILE));
         if (idx)
@@ -798,15 +798,17 @@ __global__ __launch_bounds__(256) void rs_onesweep_kernel(const uint32_t *__rest
     if (stamps && tid == 0 && bid < (uint32_t)STAMP_SLOTS) stamps[bid] = make_uint4(t0, t_rank, t_lb, stamp_now());
 }
 
-template <int ITEMS, int LBW>
+constexpr int RS_LBW = 16;  // the onesweep look-back window; 1, 32 and 64 measured no faster
+
+template <int ITEMS>
 static void launch_radix_sort_onesweep(hipStream_t s, SortScratch &sc, uint32_t n, int passes, bool keyed,
                                        const uint32_t *keys0, const SortGather *gather) {
     const uint32_t nb = div_up(n, (uint32_t)ITEMS * 256u);
     (void)hipMemsetAsync(sc.ctrl, 0, sizeof(uint32_t) * (RS_CTRL_WORDS + (size_t)passes * nb * RS_BINS), s);
     const uint32_t hb = min(div_up(n, 256u * 8u), 2048u);
-    uint4 *stamps = tuning("stamp", 0) ? stamp_buffer(2) : nullptr;
-    const uint32_t pat = (uint32_t)tuning("lb_patience", 1 << 16);
-    const int force = tuning("lb_force", 0);
+    uint4 *stamps = tuning(K_stamp) ? stamp_buffer(2) : nullptr;
+    const uint32_t pat = LB_PATIENCE;
+    const int force = tuning(K_lb_force);
     rs_multi_hist_kernel<<<max(hb, 1u), 256, 0, s>>>(keys0, n, passes, sc.ctrl,
                                                     stamps ? stamp_buffer(3) : nullptr);
     rs_hist_scan_kernel<<<1, 256, 0, s>>>(sc.ctrl, passes);
@@ -817,10 +819,10 @@ static void launch_radix_sort_onesweep(hipStream_t s, SortScratch &sc, uint32_t 
         SortGather ga;
         if (p == passes - 1 && gather) ga = *gather;
         if (p == 0 && !keyed)
-            rs_onesweep_kernel<true, ITEMS, LBW><<<nb, 256, 0, s>>>(kin, nullptr, n, p, sc.ctrl, st, sc.k[out],
+            rs_onesweep_kernel<true, ITEMS, RS_LBW><<<nb, 256, 0, s>>>(kin, nullptr, n, p, sc.ctrl, st, sc.k[out],
                                                                sc.v[out], stamps, ga, pat, force);
         else
-            rs_onesweep_kernel<false, ITEMS, LBW><<<nb, 256, 0, s>>>(kin, sc.v[in], n, p, sc.ctrl, st, sc.k[out],
+            rs_onesweep_kernel<false, ITEMS, RS_LBW><<<nb, 256, 0, s>>>(kin, sc.v[in], n, p, sc.ctrl, st, sc.k[out],
                                                                 sc.v[out], stamps, ga, pat, force);
     }
 }
@@ -837,14 +839,13 @@ static void launch_radix_sort_multi(hipStream_t s, SortScratch &sc, uint32_t n, 
     const int d0 = dbits0 > 0 ? dbits0 : dbits;
     KT *k[2] = {reinterpret_cast<KT *>(sc.k[0]), reinterpret_cast<KT *>(sc.k[1])};
     const uint32_t nb = div_up(n, (uint32_t)ITEMS * 256u);  // <= the RS_TILE block count carve_sort sized
-    // "rs_cscan" 1 (default): the one-launch count scan (look-back counts < 2^30); 0: the three-launch column scan
-    const bool one = BINS != RS_BINS || (tuning("rs_cscan", 1) != 0 && n <= RS_ONESWEEP_MAX_N);
+    const bool one = BINS != RS_BINS || (tuning(K_rs_cscan) != 0 && n <= RS_ONESWEEP_MAX_N);
     // count-scan rows per workgroup: 64 for long 256-bin matrices ("rs_cs64"; the 16-bit tile sort at 16 keys per
     // thread has ~9.6 k rows at cfg 5), else 32
     const uint32_t CS_C = (BINS == RS_BINS && nb > 4096) ? 64u : 32u;
     const uint32_t nch = div_up(nb, CS_C);  // <= RS_MAX_PASSES * nb_os rows of sc.status per pass
-    const uint32_t pat = (uint32_t)tuning("lb_patience", 1 << 16);
-    const int force = tuning("lb_force", 0);
+    const uint32_t pat = LB_PATIENCE;
+    const int force = tuning(K_lb_force);
     for (int p = 0; p < passes; p++) {
         const int shift = p == 0 ? 0 : d0 + dbits * (p - 1), in = (p + flip) & 1, out = (p + 1 + flip) & 1;
         const uint32_t dmask = (1u << (p == 0 ? d0 : dbits)) - 1u;
@@ -888,31 +889,22 @@ static void launch_radix_sort_multi(hipStream_t s, SortScratch &sc, uint32_t n, 
     }
 }
 
+// keys per thread of the multi-kernel path: 16 up to 8M keys, else 32 (fewer blocks, longer digit runs per block;
+// cfg 5: the 5M-key depth sort 0.313 -> 0.275 ms with 16, the 48M-key tile sort 0.667 -> 0.723 ms)
+static bool rs_items32(uint32_t n) { return n > (8u << 20); }
+
 bool launch_radix_sort(hipStream_t s, SortScratch &sc, uint32_t n, int nbits, bool keyed, const uint32_t *keys0,
                        const SortGather *gather) {
     if (n == 0) return gather != nullptr;
     if (!keys0) keys0 = sc.k[0];
     const int passes = radix_passes(nbits);
-    // onesweep knob: bit 0 = depth-size sorts (nbits == 32), bit 1 = tile sorts
-    const int os = tuning("onesweep", 1);
-    // measured (depth sorts, with the permuted gather): onesweep 0.121 / 0.378 ms at 1 M / 5 M keys against
-    // 0.183 / 0.329 for the multi-kernel path (32 keys per thread); linear fits cross near 3.2 M keys
-    const uint32_t os_max = (uint32_t)tuning("onesweep_max_n", 3 << 20);
+    const int os = tuning(K_onesweep);
+    const uint32_t os_max = (uint32_t)tuning(K_onesweep_max_n);
     if (n <= RS_ONESWEEP_MAX_N && n <= os_max && passes <= RS_MAX_PASSES && (os & (nbits == 32 ? 1 : 2))) {
-        // 8-/32-key tiles measured slower
-        const int lbw = tuning("lbw", 16);
-        if (lbw >= 64) launch_radix_sort_onesweep<RS_ITEMS, 64>(s, sc, n, passes, keyed, keys0, gather);
-        else if (lbw >= 32) launch_radix_sort_onesweep<RS_ITEMS, 32>(s, sc, n, passes, keyed, keys0, gather);
-        else if (lbw >= 16) launch_radix_sort_onesweep<RS_ITEMS, 16>(s, sc, n, passes, keyed, keys0, gather);
-        else launch_radix_sort_onesweep<RS_ITEMS, 1>(s, sc, n, passes, keyed, keys0, gather);
+        launch_radix_sort_onesweep<RS_ITEMS>(s, sc, n, passes, keyed, keys0, gather);  // 8-/32-key tiles measured slower
         return gather != nullptr;
     }
-    // "rs_items": keys per thread of the multi-kernel path, 16 or 32 (fewer blocks, longer digit runs per block);
-    // 0 (default): 16 up to 8M keys, else 32 (cfg 5: the 5M-key depth sort 0.313 -> 0.275 ms with 16, the 48M-key
-    // tile sort 0.667 -> 0.723 ms)
-    int items = tuning("rs_items", 0);
-    if (items == 0) items = n <= (8u << 20) ? 16 : 32;
-    if (items >= 32) launch_radix_sort_multi<32>(s, sc, n, passes, keyed, keys0, gather);
+    if (rs_items32(n)) launch_radix_sort_multi<32>(s, sc, n, passes, keyed, keys0, gather);
     else launch_radix_sort_multi<RS_ITEMS>(s, sc, n, passes, keyed, keys0, gather);
     return gather != nullptr;
 }
@@ -927,13 +919,12 @@ void launch_depth_sort_rel(hipStream_t s, SortScratch &sc, uint32_t n, const uin
     const int passes = (bits + 8) / 9;
     const int dbits = (bits + passes - 1) / passes;
     const int flip = passes & 1;
-    int items = tuning("rs_items", 0);
-    if (items == 0) items = n <= (8u << 20) ? 16 : 32;
+    const bool items32 = rs_items32(n);
     if (dbits > 8) {
-        if (items >= 32) launch_radix_sort_multi<32, uint32_t, 512>(s, sc, n, passes, false, keys0, gather, dbits, kbase, kcap, flip);
+        if (items32) launch_radix_sort_multi<32, uint32_t, 512>(s, sc, n, passes, false, keys0, gather, dbits, kbase, kcap, flip);
         else launch_radix_sort_multi<RS_ITEMS, uint32_t, 512>(s, sc, n, passes, false, keys0, gather, dbits, kbase, kcap, flip);
     } else {
-        if (items >= 32) launch_radix_sort_multi<32>(s, sc, n, passes, false, keys0, gather, dbits, kbase, kcap, flip);
+        if (items32) launch_radix_sort_multi<32>(s, sc, n, passes, false, keys0, gather, dbits, kbase, kcap, flip);
         else launch_radix_sort_multi<RS_ITEMS>(s, sc, n, passes, false, keys0, gather, dbits, kbase, kcap, flip);
     }
 }
@@ -943,13 +934,10 @@ void launch_radix_sort16(hipStream_t s, SortScratch &sc, uint32_t n, int dbits, 
     const uint16_t *k0 = reinterpret_cast<const uint16_t *>(sc.k[0]);
     // 16 keys per thread at every size for the 16-bit tile keys (cfg 5, 39.5 M keys: 0.454 -> 0.427 ms against 32, whose
     // scatter holds 148 VGPRs, 3 waves per SIMD; profiles/r5ax_ab_rs_items_cfg5.txt)
-    int items = tuning("rs_items", 0);
-    if (items == 0) items = 16;
-    // "tile_lo_short" 1: the first pass takes the short digit (15-bit keys: 7 + 8 bits instead of 8 + 7), so its 128
-    // digit runs per block are twice as long as 256 would be
-    const int d0 = (tuning("tile_lo_short", 1) && passes >= 2 && bits < dbits * passes) ? bits - dbits * (passes - 1) : 0;
-    if (items >= 32) launch_radix_sort_multi<32, uint16_t>(s, sc, n, passes, false, k0, nullptr, dbits, 0, 0, 0, d0);
-    else launch_radix_sort_multi<RS_ITEMS, uint16_t>(s, sc, n, passes, false, k0, nullptr, dbits, 0, 0, 0, d0);
+    // the first pass takes the short digit (15-bit keys: 7 + 8 bits instead of 8 + 7), so its 128 digit runs per block
+    // are twice as long as 256 would be
+    const int d0 = (passes >= 2 && bits < dbits * passes) ? bits - dbits * (passes - 1) : 0;
+    launch_radix_sort_multi<RS_ITEMS, uint16_t>(s, sc, n, passes, false, k0, nullptr, dbits, 0, 0, 0, d0);
 }
 
 }  // namespace gsr

@@ -299,7 +299,7 @@ __global__ __launch_bounds__(64) void ssim_fwd_stream_kernel(int H, int W, const
 // "ssim_stream" 1 (default): the streaming forward (1080p x 3: 59-68 us against 86 for the tiled kernel).  A streaming
 // backward of the same shape measured 92 us against the tiled backward's 72 (its per-row LDS round trips at 5 waves
 // per SIMD cost more than the tiled kernel's halo re-reads) and was removed.
-static bool ssim_stream_fwd() { return tuning("ssim_stream", 1) != 0; }
+static bool ssim_stream_fwd() { return tuning(K_ssim_stream) != 0; }
 
 static SsimWindow ssim_window() {
     SsimWindow w;

@@ -508,13 +508,19 @@ const char *gsr_stage_name(int stage);
 int gsr_stage_times(double *total_ms, int64_t *calls, int max_stages);
 void gsr_reset_stage_times(void);
 
-/* Internal tuning knobs for A/B measurements (e.g. "bwd_occ4"); unknown names are ignored by kernels. */
-void gsr_set_tuning(const char *name, int value);
+/* Internal tuning knobs for A/B measurements (e.g. "bucket"; the list is gsr_tuning_name).  GSR_OK, or GSR_ERR_ARG
+ * with gsr_last_error() naming the knob when the library has none of that name (the read-only "stat_*" names
+ * included): nothing is stored then. */
+int gsr_set_tuning(const char *name, int value);
 /* gsr_set_tuning(name, GSR_TUNING_UNSET) forgets the knob: its built-in default applies again. */
 #define GSR_TUNING_UNSET (-2147483647 - 1)
-/* A knob's value (default_value if never set).  The forward also records diagnostics here under "stat_*" names
- * (e.g. "stat_depth_passes": the radix passes of the last depth sort, 0 on the bucket path). */
+/* A knob's value (default_value if not set, or unknown).  The forward's read-only statistics are read here too, under
+ * "stat_*" names ("stat_depth_passes": the radix passes of the last depth sort, 0 on the bucket path). */
 int gsr_get_tuning(const char *name, int default_value);
+/* The knobs: their number, and knob i's name and built-in default ("" and 0 outside [0, gsr_num_tunings())). */
+int gsr_num_tunings(void);
+const char *gsr_tuning_name(int i);
+int gsr_tuning_default(int i);
 
 /* Diagnostics: with the "stamp" knob set, the composite kernels record one (start, end, HW_ID, XCC_ID)
  * uint32 quadruple per launch slot (start/end on the 100 MHz real-time clock).  which = 0: render_fwd,

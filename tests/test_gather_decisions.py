@@ -161,11 +161,8 @@ def test_split_stages_with_unmarked_composite(scene):
     st = forward_raw(*scene["args"])[-1]
     backward_raw(st, rs, d1, i1)  # marks the left half's Gaussians
     out = {k: torch.full((n, w), float("nan"), device=dc.device) for k, w in widths.items()}
-    try:
-        _native.set_tuning("bwd_live", 0)
+    with _native.tuned(bwd_live=0):
         backward_chunked(st, rs, dc, di, [(0, n, out)], after_composite=lambda: _native.set_tuning("bwd_live", 1))
-    finally:
-        _native.unset_tuning("bwd_live")
     fresh = backward_raw(forward_raw(*scene["args"])[-1], rs, dc, di, absgrad=True)
     torch.cuda.synchronize()
     for k in widths:

@@ -467,15 +467,11 @@ def test_exact_culling_is_bitwise_invisible(gpu_device):
     inp = scene_inputs(200_000, 1280, 720, sh_degree=3, seed=2)
     dc, di = upstream(1280, 720, 2)
     # segment boundaries are counted in instances, which culling removes: compare one-walk backwards
-    try:
-        _native.set_tuning("bwd_seg", 0)
-        _native.set_tuning("cull", 0)
-        full = run_hip(inp, gpu_device, dc, di)
-        _native.set_tuning("cull", 1)
-        cull = run_hip(inp, gpu_device, dc, di)
-    finally:
-        _native.unset_tuning("cull")
-        _native.unset_tuning("bwd_seg")
+    with _native.tuned(bwd_seg=0):
+        with _native.tuned(cull=0):
+            full = run_hip(inp, gpu_device, dc, di)
+        with _native.tuned(cull=1):
+            cull = run_hip(inp, gpu_device, dc, di)
     assert cull["state"].num_rendered < 0.8 * full["state"].num_rendered
     for k in ("color", "invdepth", "radii"):
         assert np.array_equal(cull[k], full[k]), k
@@ -593,14 +589,10 @@ def test_per_xcd_lpt_order_is_bitwise_invisible(gpu_device):
     inp = scene_inputs(150_000, 1920, 1080, sh_degree=3, seed=6, bg=(0.3, 0.6, 0.9))
     dc, di = upstream(1920, 1080, 6)
     ref = run_hip(inp, gpu_device, dc, di)
-    try:
-        _native.set_tuning("xcd_lpt", 0)
+    with _native.tuned(xcd_lpt=0):
         glob = run_hip(inp, gpu_device, dc, di)
-        _native.set_tuning("lpt", 0)
-        none = run_hip(inp, gpu_device, dc, di)
-    finally:
-        _native.unset_tuning("xcd_lpt")
-        _native.unset_tuning("lpt")
+        with _native.tuned(lpt=0):
+            none = run_hip(inp, gpu_device, dc, di)
     for alt in (glob, none):
         for k in ("color", "invdepth", "radii"):
             assert np.array_equal(ref[k], alt[k]), k
@@ -623,19 +615,12 @@ def test_composite_variants_are_bitwise_identical(gpu_device, knobs):
     from gaussian_splatting_lightning_amd import _native
     inp = scene_inputs(200_000, 1280, 720, sh_degree=3, seed=4, bg=(0.3, 0.6, 0.9))
     dc, di = upstream(1280, 720, 4)
-    defaults = {"fwd_parts": 0, "fwd_whole_waves": 8, "strip_exact": 1, "bwd_parts": 0, "bwd_union": -1, "smask": 1}
-    try:
-        _native.set_tuning("bwd_seg", 0)  # 3600 tiles: the default walks segments (test_segmented_backward)
-        _native.set_tuning("bwd_parts", 1)  # the reference side: one wave per tile (the default here is 2)
+    # bwd_seg 0: at 3600 tiles the default walks segments (test_segmented_backward); bwd_parts 1: the reference side,
+    # one wave per tile (the default here is 2)
+    with _native.tuned(bwd_seg=0, bwd_parts=1):
         ref = run_hip(inp, gpu_device, dc, di)
-        for k, v in knobs.items():
-            _native.set_tuning(k, v)
-        alt = run_hip(inp, gpu_device, dc, di)
-    finally:
-        for k in knobs:
-            _native.set_tuning(k, defaults[k])
-        _native.unset_tuning("bwd_parts")
-        _native.unset_tuning("bwd_seg")
+        with _native.tuned(**knobs):
+            alt = run_hip(inp, gpu_device, dc, di)
     for k in ("color", "invdepth", "radii"):
         assert np.array_equal(ref[k], alt[k]), k
     for k in GRADS:
@@ -657,17 +642,11 @@ def test_segmented_backward(gpu_device, seg_k):
     from gaussian_splatting_lightning_amd import _native
     inp = scene_inputs(200_000, 1280, 720, sh_degree=3, seed=4, bg=(0.3, 0.6, 0.9))  # 3600 tiles
     dc, di = upstream(1280, 720, 4)
-    try:
-        _native.set_tuning("bwd_seg", 0)
-        _native.set_tuning("bwd_parts", 1)
-        ref = run_hip(inp, gpu_device, dc, di)
-        _native.set_tuning("bwd_seg", 1)
-        _native.set_tuning("seg_k", seg_k)
-        alt = run_hip(inp, gpu_device, dc, di)
-    finally:
-        _native.unset_tuning("bwd_seg")
-        _native.unset_tuning("bwd_parts")
-        _native.unset_tuning("seg_k")
+    with _native.tuned(bwd_parts=1):
+        with _native.tuned(bwd_seg=0):
+            ref = run_hip(inp, gpu_device, dc, di)
+        with _native.tuned(bwd_seg=1, seg_k=seg_k):
+            alt = run_hip(inp, gpu_device, dc, di)
     for k in ("color", "invdepth", "radii"):
         assert np.array_equal(ref[k], alt[k]), k
     errs = _seg_rel_errors(alt, ref)
@@ -689,16 +668,12 @@ def test_segmented_backward_without_checkpoints(gpu_device):
     t = {k: torch.as_tensor(inp[k], device=gpu_device) for k in ("means3D", "opacities", "scales", "rotations", "shs")}
     dct, dit = torch.as_tensor(dc, device=gpu_device), torch.as_tensor(di, device=gpu_device)
     args = (t["means3D"], t["shs"], None, t["opacities"], t["scales"], t["rotations"], None, rs)
-    try:
-        _native.set_tuning("bwd_seg", 0)
-        _native.set_tuning("bwd_parts", 1)
-        _, _, _, st = forward_raw(*args)
-        ref = backward_raw(st, rs, dct, dit)
-        _native.set_tuning("bwd_seg", 1)  # backward only: the forward wrote no checkpoints
-        alt = backward_raw(st, rs, dct, dit)
-    finally:
-        _native.unset_tuning("bwd_seg")
-        _native.unset_tuning("bwd_parts")
+    with _native.tuned(bwd_parts=1):
+        with _native.tuned(bwd_seg=0):
+            _, _, _, st = forward_raw(*args)
+            ref = backward_raw(st, rs, dct, dit)
+        with _native.tuned(bwd_seg=1):  # backward only: the forward wrote no checkpoints
+            alt = backward_raw(st, rs, dct, dit)
     for k in GRADS:
         assert torch.equal(ref[k], alt[k]), k
 
@@ -715,11 +690,8 @@ def test_long_tiles_and_depth_ties(gpu_device, n, W, H):
         inp[k][5000:5300] = inp[k][5001]
     dc, di = upstream(W, H, 23)
     from gaussian_splatting_lightning_amd import _native
-    try:
-        _native.set_tuning("bucket", 2)  # bucket binning even for these long tiles (the default picks radix)
+    with _native.tuned(bucket=2):  # bucket binning even for these long tiles (the default picks radix)
         hip = run_hip(inp, gpu_device, dc, di)
-    finally:
-        _native.unset_tuning("bucket")
     run = compare_forward(inp, hip, run_oracle(inp))
     n_tile = np.diff(hip_state_arrays(hip)["ranges"], axis=1)[:, 0]
     if W > 32:
@@ -742,11 +714,8 @@ def test_dense_tiles_fall_back_to_radix_after_speculative_count(gpu_device):
     assert hip["state"].num_rendered > 1024 * T  # the radix path was chosen
     run = compare_forward(inp, hip, run_oracle(inp))
     compare_backward(hip, run, dc, di)
-    try:
-        _native.set_tuning("bucket", 2)
+    with _native.tuned(bucket=2):
         forced = run_hip(inp, gpu_device, dc, di)
-    finally:
-        _native.unset_tuning("bucket")
     for k in ("color", "invdepth", "radii"):
         assert np.array_equal(hip[k], forced[k]), k
     for k in GRADS:
@@ -765,21 +734,11 @@ def test_binning_paths_are_bitwise_identical(gpu_device, W, H, onesweep, cscan, 
     from gaussian_splatting_lightning_amd import _native
     inp = scene_inputs(200_000 if W > 100 else 60_000, W, H, sh_degree=3, seed=6, stress_fraction=0.01)
     dc, di = upstream(W, H, 6)
-    try:
-        _native.set_tuning("bucket", 2)
-        _native.set_tuning("bk_xcd", xcd)
-        ref = run_hip(inp, gpu_device, dc, di)
-        _native.set_tuning("bucket", 0)
-        _native.set_tuning("onesweep", onesweep)
-        _native.set_tuning("rs_cscan", cscan)
-        _native.set_tuning("tile_key16", k16)
-        alt = run_hip(inp, gpu_device, dc, di)
-    finally:
-        _native.unset_tuning("tile_key16")
-        _native.unset_tuning("bucket")
-        _native.unset_tuning("onesweep")
-        _native.unset_tuning("rs_cscan")
-        _native.unset_tuning("bk_xcd")
+    with _native.tuned(bk_xcd=xcd):
+        with _native.tuned(bucket=2):
+            ref = run_hip(inp, gpu_device, dc, di)
+        with _native.tuned(bucket=0, onesweep=onesweep, rs_cscan=cscan, tile_key16=k16):
+            alt = run_hip(inp, gpu_device, dc, di)
     a, b = hip_state_arrays(ref), hip_state_arrays(alt)
     for k in ("point_list", "ranges", "tiles", "n_contrib", "tile_last", "tile_loaded"):
         assert np.array_equal(a[k], b[k]), k
@@ -796,14 +755,10 @@ def test_tile_sort_digit_width_is_invisible(gpu_device, db):
     from gaussian_splatting_lightning_amd import _native
     inp = scene_inputs(200_000, 1280, 720, sh_degree=3, seed=6, stress_fraction=0.01)
     dc, di = upstream(1280, 720, 6)
-    try:
-        _native.set_tuning("bucket", 0)
+    with _native.tuned(bucket=0):
         ref = run_hip(inp, gpu_device, dc, di)
-        _native.set_tuning("tile_db", db)
-        alt = run_hip(inp, gpu_device, dc, di)
-    finally:
-        _native.unset_tuning("bucket")
-        _native.unset_tuning("tile_db")
+        with _native.tuned(tile_db=db):
+            alt = run_hip(inp, gpu_device, dc, di)
     a, b = hip_state_arrays(ref), hip_state_arrays(alt)
     for k in ("point_list", "ranges", "n_contrib"):
         assert np.array_equal(a[k], b[k]), k
@@ -822,19 +777,13 @@ def test_relative_depth_sort_is_bitwise_the_32bit_one(gpu_device, n, depth_scale
     if depth_scale != 1.0:
         inp["means3D"] = inp["means3D"] * np.array([1.0, 1.0, depth_scale], np.float32)
     dc, di = upstream(960, 540, 21)
-    try:
-        _native.set_tuning("bucket", 0)
-        _native.set_tuning("onesweep_max_n", 0)
-        _native.set_tuning("depth_rel", 0)
-        ref = run_hip(inp, gpu_device, dc, di)
-        assert _native.get_tuning("stat_depth_passes") == 4
-        _native.set_tuning("depth_rel", 1)
-        alt = run_hip(inp, gpu_device, dc, di)
-        assert 1 <= _native.get_tuning("stat_depth_passes") <= 3  # the relative sort ran
-    finally:
-        _native.unset_tuning("bucket")
-        _native.unset_tuning("onesweep_max_n")
-        _native.unset_tuning("depth_rel")
+    with _native.tuned(bucket=0, onesweep_max_n=0):
+        with _native.tuned(depth_rel=0):
+            ref = run_hip(inp, gpu_device, dc, di)
+            assert _native.get_tuning("stat_depth_passes") == 4
+        with _native.tuned(depth_rel=1):
+            alt = run_hip(inp, gpu_device, dc, di)
+            assert 1 <= _native.get_tuning("stat_depth_passes") <= 3  # the relative sort ran
     a, b = hip_state_arrays(ref), hip_state_arrays(alt)
     for key in ("point_list", "ranges", "n_contrib", "tiles"):
         assert np.array_equal(a[key], b[key]), key
@@ -862,15 +811,9 @@ def test_debug_mode_is_bitwise_identical(gpu_device, bucket, os_max):
     from gaussian_splatting_lightning_amd import _native
     inp = scene_inputs(20_000, 320, 240, sh_degree=2, seed=41)
     dc, di = upstream(320, 240, 41)
-    try:
-        _native.set_tuning("bucket", bucket)
-        if os_max is not None:
-            _native.set_tuning("onesweep_max_n", os_max)
+    with _native.tuned(bucket=bucket, **({} if os_max is None else {"onesweep_max_n": os_max})):
         a = run_hip(inp, gpu_device, dc, di)
         b = run_hip(inp, gpu_device, dc, di, debug=True)
-    finally:
-        _native.unset_tuning("bucket")
-        _native.unset_tuning("onesweep_max_n")
     for k in ("color", "invdepth", "radii"):
         assert np.array_equal(a[k], b[k]), k
     for k in GRADS:
@@ -885,16 +828,10 @@ def test_lookback_fallback_is_bitwise_invisible(gpu_device, bucket, onesweep):
     from gaussian_splatting_lightning_amd import _native
     inp = scene_inputs(20_000, 320, 240, sh_degree=2, seed=43, stress_fraction=0.01)
     dc, di = upstream(320, 240, 43)
-    try:
-        _native.set_tuning("bucket", bucket)
-        _native.set_tuning("onesweep", onesweep)
+    with _native.tuned(bucket=bucket, onesweep=onesweep):
         a = run_hip(inp, gpu_device, dc, di)
-        _native.set_tuning("lb_force", 1)
-        b = run_hip(inp, gpu_device, dc, di)
-    finally:
-        _native.unset_tuning("lb_force")
-        _native.unset_tuning("bucket")
-        _native.unset_tuning("onesweep")
+        with _native.tuned(lb_force=1):
+            b = run_hip(inp, gpu_device, dc, di)
     sa, sb = hip_state_arrays(a), hip_state_arrays(b)
     for k in ("point_list", "ranges", "tiles", "n_contrib"):
         assert np.array_equal(sa[k], sb[k]), k
@@ -913,17 +850,11 @@ def test_instance_scan_width_is_invisible(gpu_device, force, nt):
     from gaussian_splatting_lightning_amd import _native
     inp = scene_inputs(70_000, 480, 320, sh_degree=1, seed=47, stress_fraction=0.01)
     dc, di = upstream(480, 320, 47)
-    try:
-        _native.set_tuning("bucket", 0)
-        _native.set_tuning("onesweep", 0)
-        _native.set_tuning("lb_force", force)
-        _native.set_tuning("scan_nt", 256)
-        a = run_hip(inp, gpu_device, dc, di)
-        _native.set_tuning("scan_nt", nt)
-        b = run_hip(inp, gpu_device, dc, di)
-    finally:
-        for k in ("scan_nt", "lb_force", "bucket", "onesweep"):
-            _native.unset_tuning(k)
+    with _native.tuned(bucket=0, onesweep=0, lb_force=force):
+        with _native.tuned(scan_nt=256):
+            a = run_hip(inp, gpu_device, dc, di)
+        with _native.tuned(scan_nt=nt):
+            b = run_hip(inp, gpu_device, dc, di)
     sa, sb = hip_state_arrays(a), hip_state_arrays(b)
     for k in ("point_list", "ranges", "tiles", "n_contrib"):
         assert np.array_equal(sa[k], sb[k]), k
@@ -1121,19 +1052,16 @@ def test_threshold_guard_band(gpu_device, case):
     g = run.backward(dc, di)
     _, nc_ref = run.image_state()
     rec = {}
-    try:
-        for guard in (0, 1):
-            _native.set_tuning("guard", guard)
+    for guard in (0, 1):
+        with _native.tuned(guard=guard):
             hip = run_hip(inp, gpu_device, dc, di)
-            nc = hip_state_arrays(hip)["n_contrib"]
-            e = {"n_contrib_mismatch_pixels": int((nc != nc_ref).sum()),
-                 "color_maxabs": float(np.abs(hip["color"] - out[0]).max())}
-            for k in GRADS:
-                if hip["grads"].get(k) is not None:
-                    e[f"grad_rel_l2_{k}"] = rel_l2(hip["grads"][k], g[k])
-            rec[f"guard{guard}"] = e
-    finally:
-        _native.set_tuning("guard", 0)
+        nc = hip_state_arrays(hip)["n_contrib"]
+        e = {"n_contrib_mismatch_pixels": int((nc != nc_ref).sum()),
+             "color_maxabs": float(np.abs(hip["color"] - out[0]).max())}
+        for k in GRADS:
+            if hip["grads"].get(k) is not None:
+                e[f"grad_rel_l2_{k}"] = rel_l2(hip["grads"][k], g[k])
+        rec[f"guard{guard}"] = e
     parity.record(_case(), "guard_band", rec)
     assert rec["guard1"]["n_contrib_mismatch_pixels"] <= rec["guard0"]["n_contrib_mismatch_pixels"], rec
     # with the guard, SURVEY A13's tolerances hold over ALL pixels and Gaussians (no flip-candidate exclusion):
@@ -1244,12 +1172,9 @@ def test_split_stage_backward_reads_the_live_flags_validity_word(gpu_device):
     _, _, _, st = forward_raw(*args)
     backward_raw(st, rs, d1, i1)  # marks the left half's Gaussians
     out = {k: torch.full((n, w), float("nan"), device=gpu_device) for k, w in widths.items()}
-    try:
-        _native.set_tuning("bwd_live", 0)  # the composite: no marks, validity word cleared
+    with _native.tuned(bwd_live=0):  # the composite: no marks, validity word cleared
         backward_chunked(st, rs, d2, i2, [(0, n, out)],
                          after_composite=lambda: _native.set_tuning("bwd_live", 1))  # the per-Gaussian pass reads it
-    finally:
-        _native.unset_tuning("bwd_live")
     _, _, _, st2 = forward_raw(*args)
     fresh = backward_raw(st2, rs, d2, i2)
     torch.cuda.synchronize()

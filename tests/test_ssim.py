@@ -69,14 +69,11 @@ def test_streaming_ssim_matches_tiled_kernels(gpu_device, shape, padding):
     from gaussian_splatting_lightning_amd import _native
     x, y = _images(*shape, seed=5)
     out = {}
-    try:
-        for mode in (0, 1):  # tiled forward, streaming forward (the default)
-            _native.set_tuning("ssim_stream", mode)
+    for mode in (0, 1):  # tiled forward, streaming forward (the default)
+        with _native.tuned(ssim_stream=mode):
             xt = torch.tensor(x, device=gpu_device, requires_grad=True)
             m = fused_ssim(xt, torch.tensor(y, device=gpu_device), padding=padding)
             (1 - m).backward()
             out[mode] = (float(m), xt.grad.cpu().numpy())
-    finally:
-        _native.unset_tuning("ssim_stream")
     assert abs(out[0][0] - out[1][0]) <= 1e-6 * max(1.0, abs(out[0][0]))
     assert np.array_equal(out[0][1], out[1][1])

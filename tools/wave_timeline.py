@@ -85,7 +85,7 @@ def main():
     _native.set_tuning("stamp", 0)
     T = ((cfg["W"] + 15) // 16) * ((cfg["H"] + 15) // 16)
     # launch slots: whole tiles (render_fwd_v6 <4, 6>) unless the image is small enough for 4 row-strip parts
-    # (launch_render_fwd's fwd_part_slots rule)
+    # (render_fwd_parts' FWD_PART_SLOTS rule)
     nfwd = T * 4 if T * 4 <= 16384 else T
     sf = _native.wave_stamps(0, nfwd)
     # backward slots: one per tile, or one per (tile, segment) work item of the segmented walk (small images); the
