@@ -121,6 +121,8 @@ class DensifyField(ctypes.Structure):
 
 
 FIELD_PLAIN, FIELD_XYZ, FIELD_SCALING, FIELD_STAT = 0, 1, 2, 3
+FIELD_OPACITY = 4  # gsr_mcmc_apply only
+MCMC_MAX_RATIO = 51  # gsr_mcmc_relocation clamps its ratios to [1, 51]
 
 
 class PlyColumn(ctypes.Structure):
@@ -157,6 +159,7 @@ EXPORTED_SYMBOLS = (
     "gsr_forward_ext", "gsr_backward_ext", "gsr_backward_abs", "gsr_bwd_scratch_bytes_abs",
     "gsr_forward_features", "gsr_backward_features", "gsr_bwd_scratch_bytes_features",
     "gsr_contributions", "gsr_contrib_scratch_bytes", "gsr_densify_classify_keep",
+    "gsr_mcmc_noise", "gsr_mcmc_relocation", "gsr_mcmc_apply",
 )
 
 _lib = None
@@ -210,6 +213,15 @@ def load(path: str | None = None):
         lib.gsr_densify_classify_keep.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_void_p]
         lib.gsr_densify_classify_keep.restype = ctypes.c_int
+    if hasattr(lib, "gsr_mcmc_noise"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
+        lib.gsr_mcmc_noise.argtypes = [ctypes.c_int64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_void_p]
+        lib.gsr_mcmc_noise.restype = ctypes.c_int
+        lib.gsr_mcmc_relocation.argtypes = [ctypes.c_int64, _fp, _fp, ctypes.c_int, _fp, _fp, ctypes.c_int64,
+                                            ctypes.c_float, _fp, _fp, ctypes.c_void_p]
+        lib.gsr_mcmc_relocation.restype = ctypes.c_int
+        lib.gsr_mcmc_apply.argtypes = [ctypes.c_int64, ctypes.c_int64, _fp, _fp, _fp, ctypes.c_float, _fp,
+                                       ctypes.POINTER(DensifyField), ctypes.c_int, ctypes.c_void_p]
+        lib.gsr_mcmc_apply.restype = ctypes.c_int
     lib.gsr_mark_visible.argtypes = [ctypes.c_int, _fp, _fp, _fp, _fp, ctypes.c_void_p]
     lib.gsr_mark_visible.restype = ctypes.c_int
     lib.gsr_sh_backward_views.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp,

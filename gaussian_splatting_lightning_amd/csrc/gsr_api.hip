@@ -1725,6 +1725,103 @@ int gsr_densify_apply(int64_t N, const void *workspace, const float *rotation, c
     return GSR_OK;
 }
 
+int gsr_mcmc_noise(int64_t N, float *xyz, const float *opacity, const float *scaling, const float *rotation,
+                   const float *z, float scale, void *stream_ptr) {
+    if (N < 0 || N > 0x7fffffffLL * 256) return fail(GSR_ERR_ARG, "mcmc noise: bad N");
+    if (!xyz || !opacity || !scaling || !rotation || !z) return fail(GSR_ERR_ARG, "mcmc noise: null array");
+    if (!aligned16(rotation)) return fail(GSR_ERR_ARG, "mcmc noise: rotation must be 16-B aligned");
+    if (N == 0) return GSR_OK;
+    McmcNoise A{};
+    A.N = N;
+    A.xyz = xyz; A.opacity = opacity; A.scaling = scaling; A.rotation = rotation; A.z = z;
+    A.scale = scale;
+    const double c = 1.0 - 0.995;  // the gate's threshold on the opacity, to double precision in two floats
+    A.gate_c_hi = (float)c;
+    A.gate_c_lo = (float)(c - (double)A.gate_c_hi);
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_mcmc_noise((hipStream_t)stream_ptr, A);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+static void mcmc_inv_sqrt(McmcValues &V) {
+    for (int k = 0; k < MCMC_MAX_RATIO; k++) V.inv_sqrt[k] = 1.0 / std::sqrt((double)(k + 1));
+}
+
+int gsr_mcmc_relocation(int64_t N, const float *opacity, const float *scaling, int activated, const int64_t *src_idx,
+                        const int32_t *ratio, int64_t n, float min_opacity, float *new_opacity, float *new_scaling,
+                        void *stream_ptr) {
+    if (N < 0 || N > 0x7fffffffLL) return fail(GSR_ERR_ARG, "mcmc relocation: 0 <= N < 2^31");
+    if (n < 0 || n > 0x7fffffffLL) return fail(GSR_ERR_ARG, "mcmc relocation: 0 <= n < 2^31");
+    if (!(min_opacity > 0.f && min_opacity < 1.f)) return fail(GSR_ERR_ARG, "mcmc relocation: min_opacity must be in (0, 1)");
+    if (!opacity || !scaling || !ratio || !new_opacity || !new_scaling)
+        return fail(GSR_ERR_ARG, "mcmc relocation: null array");
+    if (!src_idx && n > N) return fail(GSR_ERR_ARG, "mcmc relocation: n > N without src_idx");
+    if (n == 0 || N == 0) return GSR_OK;
+    McmcValues V{};
+    V.N = N; V.n = n;
+    V.opacity = opacity; V.scaling = scaling; V.src_idx = src_idx; V.ratio = ratio;
+    V.new_opacity = new_opacity; V.new_scaling = new_scaling;
+    V.op_stride = 1; V.sc_stride = 3;
+    V.activated = activated != 0;
+    V.min_opacity = min_opacity;
+    mcmc_inv_sqrt(V);
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_mcmc_values((hipStream_t)stream_ptr, V);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_mcmc_apply(int64_t N, int64_t n, const int64_t *src_idx, const int64_t *dst_idx, const int32_t *occurrences,
+                   float min_opacity, float *values, const gsr_densify_field *fields, int num_fields,
+                   void *stream_ptr) {
+    if (N < 0 || N > 0x7fffffffLL) return fail(GSR_ERR_ARG, "mcmc apply: 0 <= N < 2^31");
+    if (n < 0 || n > 0x7fffffffLL) return fail(GSR_ERR_ARG, "mcmc apply: 0 <= n < 2^31");
+    if (!(min_opacity > 0.f && min_opacity < 1.f)) return fail(GSR_ERR_ARG, "mcmc apply: min_opacity must be in (0, 1)");
+    if (num_fields < 0 || num_fields > DENSIFY_MAX_FIELDS) return fail(GSR_ERR_ARG, "mcmc apply: 0..16 fields");
+    if (!src_idx || !occurrences || !values || !fields) return fail(GSR_ERR_ARG, "mcmc apply: null input");
+    const bool add = dst_idx == nullptr;
+    McmcApply A{};
+    A.N = N; A.n = n;
+    A.src_idx = src_idx; A.dst_idx = dst_idx; A.occ = occurrences; A.values = values;
+    McmcValues V{};
+    int64_t blocks = 0;
+    int nf = 0;
+    for (int i = 0; i < num_fields; i++) {
+        const gsr_densify_field &f = fields[i];
+        if (f.width <= 0 || !f.dst || (add && !f.src)) return fail(GSR_ERR_ARG, "mcmc apply: field needs dst (add: src too), width > 0");
+        if (f.kind < GSR_FIELD_PLAIN || f.kind > GSR_FIELD_OPACITY) return fail(GSR_ERR_ARG, "mcmc apply: bad kind");
+        if ((f.kind == GSR_FIELD_OPACITY && f.width != 1) || (f.kind == GSR_FIELD_SCALING && f.width != 3))
+            return fail(GSR_ERR_ARG, "mcmc apply: opacity field width must be 1, scaling field width 3");
+        if (add && ((f.dst_exp_avg && !f.src_exp_avg) || (f.dst_exp_avg_sq && !f.src_exp_avg_sq)))
+            return fail(GSR_ERR_ARG, "mcmc apply: moment destination without source");
+        const float *cur = add ? f.src : f.dst;  // the old parameters
+        if (f.kind == GSR_FIELD_OPACITY) V.opacity = cur;
+        if (f.kind == GSR_FIELD_SCALING) V.scaling = cur;
+        if (!add && f.kind == GSR_FIELD_STAT) continue;  // relocation leaves the statistics alone
+        DensifyFieldDev &d = A.f[nf];
+        d.src = f.src; d.dst = f.dst; d.src_exp_avg = f.src_exp_avg; d.src_exp_avg_sq = f.src_exp_avg_sq;
+        d.dst_exp_avg = f.dst_exp_avg; d.dst_exp_avg_sq = f.dst_exp_avg_sq; d.width = f.width; d.kind = f.kind;
+        A.block_start[nf++] = blocks;
+        blocks += (((add ? N : 0) + n) * f.width + 255) / 256;
+    }
+    if (!V.opacity || !V.scaling) return fail(GSR_ERR_ARG, "mcmc apply: an opacity and a scaling field are required");
+    if (blocks > 0x7fffffffLL) return fail(GSR_ERR_ARG, "mcmc apply: too many elements");
+    if (N == 0 || n == 0) return GSR_OK;
+    A.num_fields = nf;
+    V.N = N; V.n = n;
+    V.src_idx = src_idx; V.occ = occurrences;
+    V.new_opacity = values; V.new_scaling = values + 1;
+    V.op_stride = 4; V.sc_stride = 4;
+    V.min_opacity = min_opacity;
+    mcmc_inv_sqrt(V);
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_mcmc_values((hipStream_t)stream_ptr, V);
+    launch_mcmc_apply((hipStream_t)stream_ptr, A, blocks);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
 static int ply_setup(PlyLaunch &p, int64_t n, int record_bytes, int big_endian, const gsr_ply_column *columns,
                      int num_columns, const float *const *fields, const int *widths, int num_fields, bool pack) {
     if (n < 0 || record_bytes <= 0 || record_bytes > 48 * 1024) return fail(GSR_ERR_ARG, "ply: bad n or record size");

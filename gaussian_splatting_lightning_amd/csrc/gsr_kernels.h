@@ -468,6 +468,42 @@ void launch_densify_classify(hipStream_t s, const DensifyParams &p);
 void launch_densify_classify_keep(hipStream_t s, const DensifyParams &p, const uint8_t *keep_mask);
 void launch_densify_apply(hipStream_t s, const DensifyApply &A, int64_t total_blocks);
 
+// ---- 3DGS-MCMC noise, relocation and growth (gsr_mcmc.hip) ----
+struct McmcNoise {
+    int64_t N;
+    float *xyz;                                       // (N,3), updated in place
+    const float *opacity, *scaling, *rotation, *z;    // raw (N) (N,3) (N,4), draws (N,3)
+    float scale;
+    float gate_c_hi, gate_c_lo;                       // 1 - 0.995 in double, split into two floats
+};
+void launch_mcmc_noise(hipStream_t s, const McmcNoise &A);
+
+constexpr int MCMC_MAX_RATIO = 51;
+struct McmcValues {
+    int64_t N, n;
+    const float *opacity, *scaling;   // (N) (N,3): raw (logit / log), or activated
+    const int64_t *src_idx;           // (n), or null: row j itself
+    const int32_t *ratio;             // (n), or null: 1 + occ[src_idx[j]]
+    const int32_t *occ;               // (N) occurrences of each row in src_idx (with ratio null)
+    float *new_opacity, *new_scaling; // row j at new_opacity + j * op_stride and new_scaling + j * sc_stride
+    int op_stride, sc_stride;         // 1 and 3 (packed (n) and (n,3)), or 4 and 4 (one (n,4) temporary)
+    int activated;
+    float min_opacity;
+    double inv_sqrt[MCMC_MAX_RATIO];  // 1 / sqrt(k + 1), formed on the host in double
+};
+void launch_mcmc_values(hipStream_t s, const McmcValues &A);
+
+struct McmcApply {
+    DensifyFieldDev f[DENSIFY_MAX_FIELDS];
+    int64_t block_start[DENSIFY_MAX_FIELDS];
+    int num_fields;
+    int64_t N, n;
+    const int64_t *src_idx, *dst_idx;  // dst_idx null: add mode (row N + j)
+    const int32_t *occ;                // (N)
+    const float *values;               // (n,4): new raw opacity, new raw scaling
+};
+void launch_mcmc_apply(hipStream_t s, const McmcApply &A, int64_t total_blocks);
+
 // ---- PLY records <-> fields (gsr_ply.hip) ----
 constexpr int PLY_MAX_COLS = 128, PLY_MAX_FIELDS = 8;
 struct PlyLaunch {

@@ -15,6 +15,9 @@ moments move in one scatter launch; the only host sync is the read-back of the t
 the outputs.  The split displacement is drawn as `normal_(0, 1)` of shape (n_split, 3) on the parameters'
 device -- the same draw `torch.normal(mean, std)` makes -- so with the same generator state the result matches
 the reference row for row.  No CPU fallback: the HIP library must load.
+
+The second strategy, 3DGS-MCMC (csrc/gsr_mcmc.hip), is at the end of the file: `inject_noise`, `relocate_dead`,
+`add_new` and `mcmc_relocation`.
 """
 from __future__ import annotations
 
@@ -27,7 +30,8 @@ from . import _native
 from .rasterizer import _stream_handle
 
 __all__ = ["PARAMETER_NAMES", "update_max_radii2D", "update_xyz_gradient", "densify_and_prune", "prune_points",
-           "accumulate_contributions", "reset_contributions", "prune_by_contribution"]
+           "accumulate_contributions", "reset_contributions", "prune_by_contribution",
+           "mcmc_relocation", "inject_noise", "relocate_dead", "add_new"]
 
 PARAMETER_NAMES = ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation")
 _KINDS = dict(xyz=_native.FIELD_XYZ, scaling=_native.FIELD_SCALING)
@@ -111,7 +115,11 @@ def _scatter_and_rebind(lib, gaussians, params, stats, optimizer, ws, z, N: int,
                       "gsr_densify_apply")
     _drop_contributions(gaussians)  # (N, ...) buffers of the rows that were: every change of N drops them
 
-    # rebind exactly as the reference does (nn.Parameter per attribute; optimizer state moved to the new key)
+    _rebind(gaussians, optimizer, new_params, new_stats, new_states)
+
+
+def _rebind(gaussians, optimizer, new_params, new_stats, new_states) -> None:
+    """Rebind exactly as the reference does (nn.Parameter per attribute; optimizer state moved to the new key)."""
     for k in PARAMETER_NAMES:
         setattr(gaussians, f"_{k}", nn.Parameter(new_params[k]))
     for k in _STATS:
@@ -280,3 +288,210 @@ def prune_by_contribution(gaussians, score="wmax", threshold: Optional[float] = 
         keep = torch.zeros(N, dtype=torch.bool, device=values.device)
         keep[order[:n_keep]] = True
     return prune_points(gaussians, keep.to(gaussians._xyz.device), optimizer=optimizer)
+
+
+# ---- 3DGS-MCMC (Kheradmand et al., NeurIPS 2024; gsplat's MCMCStrategy) on the kernels of csrc/gsr_mcmc.hip ----
+# A training loop calls inject_noise after every optimizer step and, every refine interval, relocate_dead and then
+# add_new.  MCMC's opacity and scale regularisers are two mean() calls in the loss and stay in torch.
+_MCMC_KINDS = dict(opacity=_native.FIELD_OPACITY, scaling=_native.FIELD_SCALING)
+_MULTINOMIAL_MAX = 2 ** 24  # torch.multinomial's limit on the number of categories
+
+
+def _mcmc_params(gaussians, what: str):
+    params = {k: getattr(gaussians, f"_{k}") for k in PARAMETER_NAMES}
+    N = int(params["xyz"].shape[0])
+    for k, t in params.items():
+        if t.shape[0] != N or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"{what}: _{k} must be a contiguous fp32 (N, ...) tensor")
+    for k, shape in (("xyz", (N, 3)), ("opacity", (N, 1)), ("scaling", (N, 3)), ("rotation", (N, 4))):
+        if tuple(params[k].shape) != shape:
+            raise RuntimeError(f"{what}: _{k} must have shape {shape}, got {tuple(params[k].shape)}")
+    return params, N
+
+
+def _need_gpu(params, what: str) -> None:
+    """The last check before any launch: the arguments were valid, and there is no CPU path."""
+    dev = params["xyz"].device
+    if dev.type != "cuda" or any(t.device != dev for t in params.values()):
+        raise RuntimeError(f"{what}: the Gaussians must live on the GPU")
+
+
+def _check_min_opacity(min_opacity: float, what: str) -> float:
+    if not 0.0 < float(min_opacity) < 1.0:
+        raise RuntimeError(f"{what}: min_opacity must be in (0, 1)")
+    return float(min_opacity)
+
+
+def _draw_sources(probs: torch.Tensor, n: int, generator, multinomial_max: int = _MULTINOMIAL_MAX) -> torch.Tensor:
+    """n indices into probs (M,), drawn with replacement with probability proportional to probs:
+    torch.multinomial up to its 2^24 categories, the inverse of the cumulative sum (float64) above."""
+    if probs.shape[0] <= multinomial_max:
+        return torch.multinomial(probs, n, replacement=True, generator=generator)
+    cdf = torch.cumsum(probs.double(), 0)
+    u = torch.rand(n, dtype=torch.float64, device=probs.device, generator=generator) * cdf[-1]
+    return torch.searchsorted(cdf, u, right=True).clamp_(max=probs.shape[0] - 1)
+
+
+def _check_sampled(sampled_idx, n: int, N: int, dev, what: str) -> torch.Tensor:
+    if not torch.is_tensor(sampled_idx) or tuple(sampled_idx.shape) != (n,) or sampled_idx.dtype != torch.int64:
+        raise RuntimeError(f"{what}: sampled_idx must be an int64 tensor of shape ({n},)")
+    if n and (int(sampled_idx.min()) < 0 or int(sampled_idx.max()) >= N):
+        raise RuntimeError(f"{what}: sampled_idx out of range [0, {N})")
+    return sampled_idx.to(dev).contiguous()
+
+
+def _mcmc_fields(params, optimizer, n_out, in_place: bool):
+    """The gsr_densify_field list of the six parameters (with their Adam moments when `optimizer` holds them), in
+    place (dst = the tensors themselves) or into new tensors of n_out rows."""
+    dev = params["xyz"].device
+    fields, new_params, new_states, keep = [], {}, {}, []
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    for k in PARAMETER_NAMES:
+        src = params[k]
+        dst = src if in_place else torch.empty((n_out,) + tuple(src.shape[1:]), dtype=torch.float32, device=dev)
+        new_params[k] = dst
+        m_src = v_src = m_dst = v_dst = None
+        if optimizer is not None:
+            group = _group_for(optimizer, k, src)
+            st = optimizer.state.get(group["params"][0], None) if group is not None else None
+            if st is not None and "exp_avg" in st:
+                m_src, v_src = st["exp_avg"], st["exp_avg_sq"]
+                for t in (m_src, v_src):
+                    if t.shape != src.shape or t.dtype != torch.float32 or t.device != dev:
+                        raise RuntimeError(f"optimizer state of {k!r} does not match its parameter")
+                if in_place:
+                    if not (m_src.is_contiguous() and v_src.is_contiguous()):
+                        raise RuntimeError(f"optimizer state of {k!r} must be contiguous")
+                    m_dst, v_dst = m_src, v_src
+                else:
+                    m_src, v_src = m_src.contiguous(), v_src.contiguous()
+                    m_dst, v_dst = torch.empty_like(dst), torch.empty_like(dst)
+                new_states[k] = (group, st, m_dst, v_dst)
+                keep += [m_src, v_src]
+            elif group is not None:
+                new_states[k] = (group, None, None, None)
+        fields.append(_native.DensifyField(src.data_ptr(), dst.data_ptr(), ptr(m_src), ptr(v_src), ptr(m_dst),
+                                           ptr(v_dst), src[0].numel(), _MCMC_KINDS.get(k, _native.FIELD_PLAIN)))
+    return fields, new_params, new_states, keep
+
+
+@torch.no_grad()
+def mcmc_relocation(opacities: torch.Tensor, scales: torch.Tensor, ratios: torch.Tensor):
+    """gsplat's compute_relocation: (new_opacities (n,), new_scales (n,3)) of activated opacities (n,) or (n,1), scales
+    (n,3) and integer ratios (n,) (clamped to [1, 51]): o' = 1 - (1 - o)^(1/r), scales times
+    c = o / sum_{k<r} C(r,k+1) (-1)^k o'^(k+1) / sqrt(k+1).  new_opacities has the shape of opacities."""
+    n = int(scales.shape[0]) if torch.is_tensor(scales) and scales.dim() == 2 else -1
+    if n < 0 or tuple(scales.shape) != (n, 3) or not torch.is_tensor(opacities) or opacities.numel() != n \
+            or opacities.dim() not in (1, 2) or not torch.is_tensor(ratios) or tuple(ratios.shape) != (n,):
+        raise RuntimeError("mcmc_relocation: opacities (n,) or (n,1), scales (n,3) and ratios (n,) are required")
+    if opacities.dtype != torch.float32 or scales.dtype != torch.float32:
+        raise RuntimeError("mcmc_relocation: opacities and scales must be float32")
+    if ratios.dtype.is_floating_point or ratios.dtype == torch.bool:
+        raise RuntimeError("mcmc_relocation: ratios must be an integer tensor")
+    dev = scales.device
+    if dev.type != "cuda" or opacities.device != dev or ratios.device != dev:
+        raise RuntimeError("mcmc_relocation: the tensors must live on one GPU")
+    lib = _native.load()
+    o, s = opacities.detach().contiguous(), scales.detach().contiguous()
+    r = ratios.clamp(1, _native.MCMC_MAX_RATIO).to(torch.int32).contiguous()
+    new_o, new_s = torch.empty_like(o), torch.empty_like(s)
+    if n:
+        _native.check(lib.gsr_mcmc_relocation(n, o.data_ptr(), s.data_ptr(), 1, None, r.data_ptr(), n, 0.5,
+                                              new_o.data_ptr(), new_s.data_ptr(), _stream_handle(dev)),
+                      "gsr_mcmc_relocation")
+    return new_o, new_s
+
+
+@torch.no_grad()
+def inject_noise(gaussians, scale: float, noise: Optional[torch.Tensor] = None,
+                 generator: Optional[torch.Generator] = None) -> None:
+    """gsplat's inject_noise_to_position in one launch, in place on gaussians._xyz:
+    xyz += Sigma (z * gate * scale), Sigma = R(q) diag(exp(scaling)^2) R(q)^T, gate = sigmoid(100 ((1 - o) - 0.995)).
+    scale: the xyz learning rate times the noise learning rate (gsplat: 5e5).  noise: the (N,3) standard normal draws
+    z, drawn here with `generator` when not given."""
+    params, N = _mcmc_params(gaussians, "inject_noise")
+    dev = params["xyz"].device
+    if noise is None:
+        noise = torch.empty((N, 3), dtype=torch.float32, device=dev).normal_(0.0, 1.0, generator=generator)
+    elif not torch.is_tensor(noise) or tuple(noise.shape) != (N, 3) or noise.dtype != torch.float32 \
+            or noise.device != dev or not noise.is_contiguous():
+        raise RuntimeError(f"inject_noise: noise must be a contiguous fp32 ({N}, 3) tensor on the parameters' device")
+    _need_gpu(params, "inject_noise")
+    if N == 0:
+        return
+    _native.check(_native.load().gsr_mcmc_noise(N, params["xyz"].data_ptr(), params["opacity"].data_ptr(),
+                                                params["scaling"].data_ptr(), params["rotation"].data_ptr(),
+                                                noise.data_ptr(), float(scale), _stream_handle(dev)), "gsr_mcmc_noise")
+
+
+@torch.no_grad()
+def relocate_dead(gaussians, min_opacity: float = 0.005, optimizer=None,
+                  generator: Optional[torch.Generator] = None, sampled_idx: Optional[torch.Tensor] = None) -> int:
+    """gsplat's relocate: every dead Gaussian (sigmoid(opacity) <= min_opacity) becomes a copy of an alive one drawn
+    with probability proportional to its opacity; a source drawn k times gets the relocation values of ratio k + 1, and
+    its Adam moments are zeroed (with `optimizer`).  In place: the parameter tensors, and so the optimizer's state keys,
+    keep their identity.  sampled_idx (n_dead,) int64 pins the source rows (alive rows of [0, N)).  Returns the number
+    of relocated rows; nothing is launched when no row is dead or none is alive."""
+    params, N = _mcmc_params(gaussians, "relocate_dead")
+    min_opacity = _check_min_opacity(min_opacity, "relocate_dead")
+    dev = params["xyz"].device
+    opac = torch.sigmoid(params["opacity"].detach()).reshape(-1)
+    dead = opac <= min_opacity
+    dead_idx = dead.nonzero().squeeze(-1)
+    n = int(dead_idx.shape[0])
+    if sampled_idx is not None:
+        src = _check_sampled(sampled_idx, n, N, dev, "relocate_dead")
+        if n and bool(dead[src].any()):
+            raise RuntimeError("relocate_dead: sampled_idx names a dead row")
+    _need_gpu(params, "relocate_dead")
+    if n == 0 or n == N:
+        return 0
+    if sampled_idx is None:
+        alive_idx = (~dead).nonzero().squeeze(-1)
+        src = alive_idx[_draw_sources(opac[alive_idx], n, generator)]
+    fields, _, _, keep = _mcmc_fields(params, optimizer, N, in_place=True)
+    occ = torch.bincount(src, minlength=N).to(torch.int32)
+    values = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    arr = (_native.DensifyField * len(fields))(*fields)
+    _native.check(_native.load().gsr_mcmc_apply(N, n, src.data_ptr(), dead_idx.data_ptr(), occ.data_ptr(), min_opacity,
+                                                values.data_ptr(), arr, len(fields), _stream_handle(dev)),
+                  "gsr_mcmc_apply")
+    return n
+
+
+@torch.no_grad()
+def add_new(gaussians, cap_max: int, growth: float = 1.05, min_opacity: float = 0.005, optimizer=None,
+            generator: Optional[torch.Generator] = None, sampled_idx: Optional[torch.Tensor] = None) -> int:
+    """gsplat's add_new: n_new = max(0, min(cap_max, int(growth * N)) - N) Gaussians are appended as copies of rows
+    drawn from all rows with probability proportional to opacity; a source drawn k times (and its copies) gets the
+    relocation values of ratio k + 1.  Parameters, statistics and (with `optimizer`) the Adam state are rebound as
+    densify_and_prune rebinds them: old moments kept, new rows' moments and statistics zero; the contribution buffers
+    are dropped.  sampled_idx (n_new,) int64 pins the source rows.  Returns n_new."""
+    params, N = _mcmc_params(gaussians, "add_new")
+    min_opacity = _check_min_opacity(min_opacity, "add_new")
+    dev = params["xyz"].device
+    n = max(0, min(int(cap_max), int(growth * N)) - N)
+    if sampled_idx is not None:
+        src = _check_sampled(sampled_idx, n, N, dev, "add_new")
+    _need_gpu(params, "add_new")
+    if n == 0:
+        return 0
+    if sampled_idx is None:
+        src = _draw_sources(torch.sigmoid(params["opacity"].detach()).reshape(-1), n, generator)
+    fields, new_params, new_states, keep = _mcmc_fields(params, optimizer, N + n, in_place=False)
+    new_stats = {}
+    for k in _STATS:
+        old = _f32(getattr(gaussians, k))
+        keep.append(old)
+        new_stats[k] = torch.empty(N + n, dtype=torch.float32, device=dev)
+        fields.append(_native.DensifyField(old.data_ptr(), new_stats[k].data_ptr(), None, None, None, None, 1,
+                                           _native.FIELD_STAT))
+    occ = torch.bincount(src, minlength=N).to(torch.int32)
+    values = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    arr = (_native.DensifyField * len(fields))(*fields)
+    _native.check(_native.load().gsr_mcmc_apply(N, n, src.data_ptr(), None, occ.data_ptr(), min_opacity,
+                                                values.data_ptr(), arr, len(fields), _stream_handle(dev)),
+                  "gsr_mcmc_apply")
+    _drop_contributions(gaussians)
+    _rebind(gaussians, optimizer, new_params, new_stats, new_states)
+    return n

@@ -13,6 +13,8 @@ working: `_xyz`, `_features_dc`, `_features_rest`, `_opacity`, `_scaling`, `_rot
   (with `optimizer=` the Adam state is re-indexed in the same launch as the parameters);
 * `accumulate_contributions`, `reset_contributions`, `prune_by_contribution` -- densify.py: the
   per-Gaussian hit count / weight sum / weight max of GaussianRasterizer.contributions over a pass of views;
+* `inject_noise`, `relocate_dead`, `add_new` -- densify.py: 3DGS-MCMC's noise on the means, relocation of dead
+  Gaussians and growth under a cap, one or two launches each;
 * `reset_opacity`, `reset_max_radii2D`, `reset_xyz_gradient`, `step_sh_degree`, `ready_for_*`.
 
 `spatial_scale` is passed directly (the reference derives it from COLMAP cameras with pycolmap,
@@ -149,6 +151,21 @@ class GaussianModel(nn.Module):
                               keep_ratio: Optional[float] = None, optimizer=None) -> torch.Tensor:
         return _densify.prune_by_contribution(self, score, threshold=threshold, keep_ratio=keep_ratio,
                                               optimizer=optimizer)
+
+    # ---- 3DGS-MCMC: per-step noise, relocation of dead Gaussians, growth under a cap (densify.py) ----
+    def inject_noise(self, scale: float, noise: Optional[torch.Tensor] = None,
+                     generator: Optional[torch.Generator] = None) -> None:
+        _densify.inject_noise(self, scale, noise=noise, generator=generator)
+
+    def relocate_dead(self, min_opacity: float = 0.005, optimizer=None,
+                      generator: Optional[torch.Generator] = None, sampled_idx: Optional[torch.Tensor] = None) -> int:
+        return _densify.relocate_dead(self, min_opacity=min_opacity, optimizer=optimizer, generator=generator,
+                                      sampled_idx=sampled_idx)
+
+    def add_new(self, cap_max: int, growth: float = 1.05, min_opacity: float = 0.005, optimizer=None,
+                generator: Optional[torch.Generator] = None, sampled_idx: Optional[torch.Tensor] = None) -> int:
+        return _densify.add_new(self, cap_max, growth=growth, min_opacity=min_opacity, optimizer=optimizer,
+                                generator=generator, sampled_idx=sampled_idx)
 
     @torch.no_grad()
     def reset_opacity(self):

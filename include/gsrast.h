@@ -441,6 +441,48 @@ typedef struct gsr_densify_field {
 int gsr_densify_apply(int64_t N, const void *workspace, const float *rotation, const float *scaling, const float *z,
                       const gsr_densify_field *fields, int num_fields, void *stream);
 
+/* 3DGS-MCMC densification (Kheradmand et al., NeurIPS 2024; gsplat's MCMCStrategy) on the raw parameters the
+ * optimizer steps: opacity (N) or (N,1) logit, scaling (N,3) log, rotation (N,4) unnormalised (w,x,y,z), 16-B aligned.
+ * Only functions are added: GSR_ABI_VERSION and every struct stay as they are.  All three return GSR_ERR_ARG before any
+ * device work on a NULL required pointer, a negative count, or a min_opacity outside (0, 1), and launch nothing (GSR_OK)
+ * when there is no row to work on.
+ *
+ * gsr_mcmc_noise: xyz[g] += Sigma_g (z[g] * gate_g * scale) in place, Sigma = R(q) diag(exp(scaling)^2) R(q)^T with
+ *   q = rotation / max(|rotation|, 1e-12), gate = 1 / (1 + exp(-100 ((1 - sigmoid(opacity)) - 0.995))); z (N,3) are the
+ *   caller's standard normal draws, scale the caller's xyz learning rate times its noise learning rate. */
+int gsr_mcmc_noise(int64_t N, float *xyz, const float *opacity, const float *scaling, const float *rotation,
+                   const float *z, float scale, void *stream);
+
+/* gsr_mcmc_relocation: the values alone, for callers with their own layout.  For j in [0, n): i = src_idx[j] (j itself
+ *   when src_idx is NULL, then n <= N), r = clamp(ratio[j], 1, 51), o = sigmoid(opacity[i]), s = exp(scaling[i]):
+ *     o' = 1 - (1 - o)^(1/r),  c = o / sum_{k<r} C(r,k+1) (-1)^k o'^(k+1) / sqrt(k+1)
+ *     new_opacity[j] = logit(clamp(o', min_opacity, 1 - 2^-23)),  new_scaling[j] = log(c s)
+ *   ratio[j] is 1 + the number of times row src_idx[j] occurs in src_idx.  activated != 0: opacity and scaling hold
+ *   sigmoid / exp values already and the outputs are o' (not clamped) and c s (gsplat's compute_relocation).  o' is
+ *   formed in fp32 as -expm1f(log1pf(-o) / r); the alternating sum is accumulated in fp64.  A src_idx[j] outside [0, N)
+ *   is skipped (its outputs are not written). */
+int gsr_mcmc_relocation(int64_t N, const float *opacity, const float *scaling, int activated, const int64_t *src_idx,
+                        const int32_t *ratio, int64_t n, float min_opacity, float *new_opacity, float *new_scaling,
+                        void *stream);
+
+/* gsr_mcmc_apply: relocation or growth of every field (gsr_densify_field; kind GSR_FIELD_OPACITY, width 1, and kind
+ *   GSR_FIELD_SCALING, width 3, must both be among them) in two launches: the values above from the old parameters into
+ *   `values` (n * 4 floats of device scratch), then one launch that moves the rows.  occurrences (N int32): how often
+ *   each row occurs in src_idx (an integer histogram such as torch.bincount); the ratio of source i is 1 + occurrences[i].
+ *     dst_idx != NULL, relocate, in place on each field's dst (N, width) (src is ignored): every distinct source row
+ *       gets its new opacity and scaling, row dst_idx[j] becomes a copy of the updated row src_idx[j] in every
+ *       parameter, dst_exp_avg / dst_exp_avg_sq are zeroed at the source rows and kept elsewhere, STAT fields are not
+ *       touched.  No row may be both a source and a destination, and no destination may repeat.
+ *     dst_idx == NULL, add, from src (N, width) into dst (N + n, width): rows [0, N) are copied with the sources
+ *       updated, row N + j is a copy of the updated source j; moments of rows [0, N) are copied, moments and STAT fields
+ *       of the new rows are zero.
+ *   Duplicate sources store identical bits, so the result is deterministic; no atomics.  A src_idx[j] or dst_idx[j]
+ *   outside [0, N) is skipped (add: that new row is zero-filled).  GSR_ERR_ARG also on a field of width <= 0, a field
+ *   without dst (add: without src), more than 16 fields, or a missing opacity / scaling field. */
+enum { GSR_FIELD_OPACITY = 4 };
+int gsr_mcmc_apply(int64_t N, int64_t n, const int64_t *src_idx, const int64_t *dst_idx, const int32_t *occurrences,
+                   float min_opacity, float *values, const gsr_densify_field *fields, int num_fields, void *stream);
+
 /* PLY vertex records <-> parameter fields (the 3DGS checkpoint of gaussian_model.py:112-171 and
  * third_party/.../gaussian_model.py:239-314).  `records` are n fixed-size records of record_bytes each, on the
  * device; `columns` (host array, destination order: field after field, column after column) give each
