@@ -1895,6 +1895,10 @@ int gsr_knn_mean_dist2(int64_t n, const float *points, float *out, void *workspa
     return GSR_OK;
 }
 
+// padding="valid" counts the map cropped by 5 px a side: both extents must exceed 10 (a product of two negative
+// extents is positive, so the count's sign does not say this).
+static bool ssim_counts_a_pixel(int H, int W, int valid_padding) { return !valid_padding || (H > 10 && W > 10); }
+
 size_t gsr_ssim_num_partials(int planes, int H, int W) {
     return (planes > 0 && H > 0 && W > 0) ? ssim_num_partials(planes, H, W) : 0;
 }
@@ -1907,6 +1911,8 @@ int gsr_ssim_forward(int planes, int H, int W, const float *img1, const float *i
     if (!img1 || !img2 || !partial_sums) return fail(GSR_ERR_ARG, "ssim: null argument");
     if ((dm_dmu1 == nullptr) != (dm_dsigma1_sq == nullptr) || (dm_dmu1 == nullptr) != (dm_dsigma12 == nullptr))
         return fail(GSR_ERR_ARG, "ssim: derivative maps must be all given or all NULL");
+    if (!ssim_counts_a_pixel(H, W, valid_padding))
+        return fail(GSR_ERR_ARG, "ssim: image smaller than the valid window");
     hipStream_t s = (hipStream_t)stream_ptr;
     StreamDeviceGuard device_guard(s);
     launch_ssim_forward(s, planes, H, W, img1, img2, valid_padding, partial_sums, dm_dmu1, dm_dsigma1_sq, dm_dsigma12);
@@ -1918,11 +1924,13 @@ int gsr_ssim_backward(int planes, int H, int W, const float *img1, const float *
                       const float *dL_dmean, const float *dm_dmu1, const float *dm_dsigma1_sq,
                       const float *dm_dsigma12, float *dL_dimg1, void *stream_ptr) {
     if (planes <= 0 || H <= 0 || W <= 0) return fail(GSR_ERR_ARG, "ssim: empty image");
+    if ((int64_t)planes * H * W > 0x7fffffffLL) return fail(GSR_ERR_ARG, "ssim: image too large");
     if (planes > 65535) return fail(GSR_ERR_ARG, "ssim: too many planes");
     if (!img1 || !img2 || !dL_dmean || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg1)
         return fail(GSR_ERR_ARG, "ssim: null argument");
+    if (!ssim_counts_a_pixel(H, W, valid_padding))
+        return fail(GSR_ERR_ARG, "ssim: image smaller than the valid window");
     const int64_t counted = (int64_t)planes * (valid_padding ? (int64_t)(H - 10) * (W - 10) : (int64_t)H * W);
-    if (counted <= 0) return fail(GSR_ERR_ARG, "ssim: image smaller than the valid window");
     hipStream_t s = (hipStream_t)stream_ptr;
     StreamDeviceGuard device_guard(s);
     launch_ssim_backward(s, planes, H, W, img1, img2, valid_padding, dL_dmean, (float)(1.0 / (double)counted), dm_dmu1,

@@ -35,12 +35,14 @@ class _FusedSSIM(torch.autograd.Function):
             raise RuntimeError(f"img1 {tuple(x.shape)} and img2 {tuple(y.shape)} differ")
         B, C, H, W = x.shape
         planes = B * C
-        valid = 1 if padding == "valid" else 0
         if padding not in ("same", "valid"):
             raise ValueError(f"padding must be 'same' or 'valid', got {padding!r}")
+        valid = 1 if padding == "valid" else 0
+        if planes * H * W == 0:
+            raise RuntimeError(f"empty image {tuple(x.shape)}")
+        if valid and not (H > 10 and W > 10):  # not the sign of (H - 10) * (W - 10): two negatives make a positive
+            raise RuntimeError(f"image {H}x{W} smaller than the SSIM window: padding='valid' counts no pixel")
         counted = planes * ((H - 10) * (W - 10) if valid else H * W)
-        if counted <= 0:
-            raise RuntimeError("image smaller than the SSIM window")
         partial = torch.empty(lib.gsr_ssim_num_partials(planes, H, W), dtype=torch.float32, device=x.device)
         need_grad = bool(train) and ctx.needs_input_grad[0]
         maps = [torch.empty_like(x) for _ in range(3)] if need_grad else [None, None, None]

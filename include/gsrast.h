@@ -326,7 +326,9 @@ int gsr_mark_visible(int P, const float *means3D, const float *viewmatrix, const
  * zero-padded "same" filtering; valid_padding = 1 averages only pixels >= 5 px from the border.
  * Forward: writes gsr_ssim_num_partials() partial sums of the SSIM map (mean = sum / counted pixels) and, when
  * the three derivative maps (planes*H*W each) are non-NULL, the per-pixel derivatives the backward needs.
- * Backward: dL_dimg1 from dL_dmean (device scalar: gradient of the mean SSIM) and the derivative maps. */
+ * Backward: dL_dimg1 from dL_dmean (device scalar: gradient of the mean SSIM) and the derivative maps.
+ * GSR_ERR_ARG, before any device work, from both: planes outside [1, 65535], planes*H*W > 2^31 - 1, a NULL argument
+ * (the forward's derivative maps: all given or all NULL), or valid_padding with H <= 10 or W <= 10 (no pixel counted). */
 size_t gsr_ssim_num_partials(int planes, int H, int W);
 int gsr_ssim_forward(int planes, int H, int W, const float *img1, const float *img2, int valid_padding,
                      float *partial_sums, float *dm_dmu1, float *dm_dsigma1_sq, float *dm_dsigma12, void *stream);

@@ -29,8 +29,10 @@ def _filt(img: np.ndarray) -> np.ndarray:
     return sum(w[k] * h[..., k:k + H, :] for k in range(11))
 
 
-def ssim(img1, img2, padding="same"):
-    """Returns (mean SSIM, dmean/dimg1) for (B,C,H,W) arrays."""
+def ssim(img1, img2, padding="same", with_term_magnitude=False):
+    """Returns (mean SSIM, dmean/dimg1) for (B,C,H,W) arrays; with_term_magnitude adds T, the largest per-pixel
+    |G*(g dmu)| + 2|x| |G*(g d11)| + |y| |G*(g d12)|: the size of the three gradient terms before they are added, which
+    is what rounding acts on where they cancel (x == y has gradient 0 and T > 0)."""
     x = np.asarray(img1, np.float64)
     y = np.asarray(img2, np.float64)
     mu1, mu2 = _filt(x), _filt(y)
@@ -48,5 +50,8 @@ def ssim(img1, img2, padding="same"):
     d12 = 2 * A / (Cc * D)
     d11 = -m / D
     dmu = 2 * mu2 * B / (Cc * D) - 2 * mu1 * m / Cc - 2 * mu1 * d11 - mu2 * d12
-    grad = _filt(g * dmu) + 2 * x * _filt(g * d11) + y * _filt(g * d12)
+    t_mu, t_11, t_12 = _filt(g * dmu), 2 * x * _filt(g * d11), y * _filt(g * d12)
+    grad = t_mu + t_11 + t_12
+    if with_term_magnitude:
+        return mean, grad, float((np.abs(t_mu) + np.abs(t_11) + np.abs(t_12)).max())
     return mean, grad

@@ -27,3 +27,4 @@ def dump() -> None:
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         json.dump(RECORD, f, indent=1, sort_keys=True)
+        f.write("\n")
