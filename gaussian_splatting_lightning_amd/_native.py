@@ -78,6 +78,18 @@ class FeaturesExt(ctypes.Structure):  # include/gsrast.h gsr_features_ext (versi
 
 
 FEATURES_MAX_C = 64  # include/gsrast.h gsr_features_ext.C
+
+
+class DistortionExt(ctypes.Structure):  # include/gsrast.h gsr_distortion_ext (versioned by struct_size)
+    _fields_ = [("struct_size", ctypes.c_size_t), ("map", ctypes.c_int), ("near_plane", ctypes.c_float),
+                ("far_plane", ctypes.c_float), ("out_distortion", _fp), ("total_weight", _fp), ("total_moment", _fp),
+                ("dL_ddistortion", _fp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=ctypes.sizeof(DistortionExt), **fields)
+
+
+DISTORTION_MAPS = {"z": 0, "ndc": 1}  # include/gsrast.h GSR_DISTORTION_Z, GSR_DISTORTION_NDC
 GSR_BUF_CONTRIB_SCRATCH = 6
 
 
@@ -158,6 +170,7 @@ EXPORTED_SYMBOLS = (
     "gsr_knn_workspace_bytes", "gsr_knn_mean_dist2", "gsr_debug_wave_stamps",
     "gsr_forward_ext", "gsr_backward_ext", "gsr_backward_abs", "gsr_bwd_scratch_bytes_abs",
     "gsr_forward_features", "gsr_backward_features", "gsr_bwd_scratch_bytes_features",
+    "gsr_forward_distortion", "gsr_backward_distortion",
     "gsr_contributions", "gsr_contrib_scratch_bytes", "gsr_densify_classify_keep",
     "gsr_mcmc_noise", "gsr_mcmc_relocation", "gsr_mcmc_apply",
 )
@@ -205,6 +218,16 @@ def load(path: str | None = None):
         lib.gsr_backward_features.restype = ctypes.c_int
         lib.gsr_bwd_scratch_bytes_features.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
         lib.gsr_bwd_scratch_bytes_features.restype = ctypes.c_size_t
+    if hasattr(lib, "gsr_forward_distortion"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
+        lib.gsr_forward_distortion.argtypes = [ctypes.POINTER(ForwardArgs), ctypes.POINTER(CompositeExt),
+                                               ctypes.POINTER(FeaturesExt), ctypes.POINTER(DistortionExt), ALLOC_FN,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
+        lib.gsr_forward_distortion.restype = ctypes.c_int
+        lib.gsr_backward_distortion.argtypes = [ctypes.POINTER(BackwardArgs), ctypes.POINTER(CompositeExt),
+                                                ctypes.POINTER(AbsgradExt), ctypes.POINTER(FeaturesExt),
+                                                ctypes.POINTER(DistortionExt), ALLOC_FN, ctypes.c_void_p,
+                                                ctypes.c_void_p]
+        lib.gsr_backward_distortion.restype = ctypes.c_int
     if hasattr(lib, "gsr_contributions"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
         lib.gsr_contributions.argtypes = [ctypes.POINTER(ContribArgs), ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p]
         lib.gsr_contributions.restype = ctypes.c_int
@@ -327,12 +350,15 @@ def _ref(struct):
     return None if struct is None else ctypes.byref(struct)
 
 
-def call_forward(lib, args, ext, feat, cb, stream, num_rendered) -> int:
+def call_forward(lib, args, ext, feat, cb, stream, num_rendered, dist=None) -> int:
     """The forward through the narrowest entry point whose extra arguments are all given: gsr_forward, gsr_forward_ext
-    (ext: CompositeExt) or gsr_forward_features (feat: FeaturesExt, ext given or None).  Which one is behaviour: at
+    (ext: CompositeExt), gsr_forward_features (feat: FeaturesExt, ext given or None) or gsr_forward_distortion (dist:
+    DistortionExt, ext and feat given or None).  Which one is behaviour: at
     P == 0 the plain call returns zeros where the ext call returns the background.  The entry point is looked up on
     `lib` here, at call time, so a patched attribute is what runs."""
     a, n = ctypes.byref(args), ctypes.byref(num_rendered)
+    if dist is not None:
+        return lib.gsr_forward_distortion(a, _ref(ext), _ref(feat), ctypes.byref(dist), cb, None, stream, n)
     if feat is not None:
         return lib.gsr_forward_features(a, _ref(ext), ctypes.byref(feat), cb, None, stream, n)
     if ext is not None:
@@ -340,10 +366,14 @@ def call_forward(lib, args, ext, feat, cb, stream, num_rendered) -> int:
     return lib.gsr_forward(a, cb, None, stream, n)
 
 
-def call_backward(lib, args, ext, absgrad, feat, cb, stream) -> int:
+def call_backward(lib, args, ext, absgrad, feat, cb, stream, dist=None) -> int:
     """The backward likewise: gsr_backward, gsr_backward_ext (ext), gsr_backward_abs (absgrad: AbsgradExt, ext given or
-    None) or gsr_backward_features (feat: FeaturesExt, ext and absgrad given or None)."""
+    None), gsr_backward_features (feat: FeaturesExt, ext and absgrad given or None) or gsr_backward_distortion (dist:
+    DistortionExt, the others given or None)."""
     a = ctypes.byref(args)
+    if dist is not None:
+        return lib.gsr_backward_distortion(a, _ref(ext), _ref(absgrad), _ref(feat), ctypes.byref(dist), cb, None,
+                                           stream)
     if feat is not None:
         return lib.gsr_backward_features(a, _ref(ext), _ref(absgrad), ctypes.byref(feat), cb, None, stream)
     if absgrad is not None:

@@ -101,6 +101,8 @@ enum Stage {
     ST_SEG_SORT,
     ST_ADAM_SH,
     ST_BACKGROUND_GRAD,
+    ST_DIST_FWD,
+    ST_DIST_BWD,
     ST_FEAT_FWD,
     ST_FEAT_BWD,
     ST_FEAT_GATHER,
@@ -112,7 +114,8 @@ const char *kStageNames[ST_COUNT] = {"preprocess", "depth_sort", "instance_scan"
                                      "expand",     "tile_sort",  "tile_ranges",   "render_fwd",
                                      "render_bwd", "big_reduce", "preprocess_bwd", "sh_views",
                                      "bucket_count", "bucket_scatter", "seg_sort", "adam_sh_views",
-                                     "background_grad", "feat_fwd", "feat_bwd", "feat_gather",
+                                     "background_grad", "distortion_fwd", "distortion_bwd",
+                                     "feat_fwd", "feat_bwd", "feat_gather",
                                      "contrib_walk", "contrib_gather"};
 
 struct Profiler {
@@ -461,6 +464,42 @@ int read_features_ext(const gsr_features_ext *x, int P, FeaturesExt &f) {
     return GSR_OK;
 }
 
+// gsr_distortion_ext as the library reads it
+struct DistortionExt {
+    bool given = false;
+    int map = 0;
+    float nearp = 0.f, farp = 0.f;
+    float *out = nullptr, *tot_w = nullptr, *tot_m = nullptr;
+    const float *dL_dD = nullptr;
+};
+// the checks both directions share: the struct's size, the map and its planes, the two totals
+int read_distortion_ext(const gsr_distortion_ext *x, DistortionExt &d) {
+    if (!x) return GSR_OK;
+    const VersionedIn<gsr_distortion_ext> in(x);
+    if (!in.covers(&gsr_distortion_ext::out_distortion))
+        return fail(GSR_ERR_ARG, "gsr_distortion_ext: struct_size ends before the first pointer field");
+    d.given = true;
+    d.map = in.get(&gsr_distortion_ext::map);
+    d.nearp = in.get(&gsr_distortion_ext::near_plane);
+    d.farp = in.get(&gsr_distortion_ext::far_plane);
+    d.out = in.get(&gsr_distortion_ext::out_distortion);
+    d.tot_w = in.get(&gsr_distortion_ext::total_weight);
+    d.tot_m = in.get(&gsr_distortion_ext::total_moment);
+    d.dL_dD = in.get(&gsr_distortion_ext::dL_ddistortion);
+    if (d.map != GSR_DISTORTION_Z && d.map != GSR_DISTORTION_NDC)
+        return fail(GSR_ERR_ARG, "gsr_distortion_ext: map must be GSR_DISTORTION_Z or GSR_DISTORTION_NDC");
+    if (d.map == GSR_DISTORTION_NDC && !(d.nearp > 0.f && d.farp > d.nearp && std::isfinite(d.farp)))
+        return fail(GSR_ERR_ARG, "gsr_distortion_ext: GSR_DISTORTION_NDC needs 0 < near_plane < far_plane");
+    if (!d.tot_w || !d.tot_m)
+        return fail(GSR_ERR_ARG, "gsr_distortion_ext: total_weight and total_moment are required");
+    return GSR_OK;
+}
+// far / (far - near) and far near / (far - near), formed in double and rounded once
+static float dist_k0(const DistortionExt &d) { return (float)((double)d.farp / ((double)d.farp - (double)d.nearp)); }
+static float dist_dscale(const DistortionExt &d) {
+    return (float)((double)d.farp * (double)d.nearp / ((double)d.farp - (double)d.nearp));
+}
+
 }  // namespace
 
 extern "C" {
@@ -607,6 +646,7 @@ struct FwdCall : RasterState {
     int dev;  // the stream's device (StreamDeviceGuard)
     CompositeExt e;
     FeaturesExt fx;
+    DistortionExt dx;
     int P;
     // the readback: this thread's pinned words and event, the sequence number awaited, and whether the preprocess
     // publishes into the words ("rb_spin") or a copy plus the event brings the counters
@@ -626,13 +666,17 @@ struct FwdCall : RasterState {
 };
 
 // The side structs and every argument check, in the order callers see their errors
-static int fwd_check_args(FwdCall &c, const gsr_composite_ext *ext, const gsr_features_ext *feat) {
+static int fwd_check_args(FwdCall &c, const gsr_composite_ext *ext, const gsr_features_ext *feat,
+                          const gsr_distortion_ext *dist) {
     gsr_forward_args *a = c.a;
     int rc = read_composite_ext(ext, a->background, c.e);
     if (rc) return rc;
     rc = read_features_ext(feat, a->P, c.fx);
     if (rc) return rc;
     if (c.fx.given && !c.fx.out_features) return fail(GSR_ERR_ARG, "gsr_features_ext: out_features is required");
+    rc = read_distortion_ext(dist, c.dx);
+    if (rc) return rc;
+    if (c.dx.given && !c.dx.out) return fail(GSR_ERR_ARG, "gsr_distortion_ext: out_distortion is required");
     rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
                       a->scales, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
                       c.e.background_image ? c.e.background_image : a->background);
@@ -657,6 +701,8 @@ static int fwd_empty_scene(FwdCall &c) {
     }
     if (a->out_invdepth) GSR_HIP(hipMemsetAsync(a->out_invdepth, 0, sizeof(float) * HW, stream));
     if (c.fx.given) GSR_HIP(hipMemsetAsync(c.fx.out_features, 0, sizeof(float) * c.fx.C * HW, stream));
+    if (c.dx.given)
+        for (float *m : {c.dx.out, c.dx.tot_w, c.dx.tot_m}) GSR_HIP(hipMemsetAsync(m, 0, sizeof(float) * HW, stream));
     return GSR_OK;
 }
 
@@ -992,6 +1038,18 @@ static int fwd_features(FwdCall &c) {
     return GSR_OK;
 }
 
+// The distortion map and its two totals, replayed likewise (tile_last = 0: zeros)
+static int fwd_distortion(FwdCall &c) {
+    hipStream_t stream = c.stream;
+    DistFwdParams dp;
+    dp.src = replay_src(c);
+    dp.depth_key = c.g.depth_key;
+    dp.map = c.dx.map; dp.k0 = dist_k0(c.dx); dp.nearp = c.dx.nearp;
+    dp.out = c.dx.out; dp.tot_w = c.dx.tot_w; dp.tot_m = c.dx.tot_m;
+    GSR_STAGE(ST_DIST_FWD, c.dbg, launch_dist_fwd(stream, dp));
+    return GSR_OK;
+}
+
 int gsr_forward(gsr_forward_args *a, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr,
                 int64_t *num_rendered) {
     return gsr_forward_ext(a, nullptr, alloc, alloc_ctx, stream_ptr, num_rendered);
@@ -1004,11 +1062,17 @@ int gsr_forward_ext(gsr_forward_args *a, const gsr_composite_ext *ext, gsr_alloc
 
 int gsr_forward_features(gsr_forward_args *a, const gsr_composite_ext *ext, const gsr_features_ext *feat,
                          gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr, int64_t *num_rendered) {
+    return gsr_forward_distortion(a, ext, feat, nullptr, alloc, alloc_ctx, stream_ptr, num_rendered);
+}
+
+int gsr_forward_distortion(gsr_forward_args *a, const gsr_composite_ext *ext, const gsr_features_ext *feat,
+                           const gsr_distortion_ext *dist, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr,
+                           int64_t *num_rendered) {
     if (!a || !alloc || !num_rendered) return fail(GSR_ERR_ARG, "null argument");
     FwdCall c{};
     c.a = a; c.alloc = alloc; c.alloc_ctx = alloc_ctx;
     c.stream = (hipStream_t)stream_ptr; c.dbg = a->debug != 0;
-    int rc = fwd_check_args(c, ext, feat);
+    int rc = fwd_check_args(c, ext, feat, dist);
     if (rc) return rc;
     // Both live in this frame across every stage: the stream's device stays current until the call returns, and an
     // early return of any stage after the preprocess launch runs ~InflightReadback (a wait for the stream) before
@@ -1030,6 +1094,7 @@ int gsr_forward_features(gsr_forward_args *a, const gsr_composite_ext *ext, cons
     if (!rc) rc = c.bucket ? fwd_bin_bucket(c) : fwd_bin_radix(c);
     if (!rc) rc = fwd_composite(c);
     if (!rc && c.fx.given) rc = fwd_features(c);
+    if (!rc && c.dx.given) rc = fwd_distortion(c);
     if (rc || !c.dbg) return rc;
     // every radix sort clears its error word (onesweep: with its control block; multi-kernel: pass 0)
     return check_lookback_flags(c.stream, c.dev, c.g.counters, c.bucket ? nullptr : c.g.sort.ctrl + RS_CTRL_ERR,
@@ -1119,6 +1184,8 @@ struct BwdCall : RasterState {
     AbsgradExt ab;
     FeaturesExt fx;
     bool feat_bwd;   // the feature work of this call: only with an upstream gradient of the feature image
+    DistortionExt dx;
+    bool dist_bwd;   // the distortion work of this call: only with an upstream gradient of the map
     int64_t g0, g1;  // the Gaussians of the per-Gaussian stage
     BwdScratch sc;
     GatherSrc src;   // what every gather of this call tests (live: null with "bwd_live" 0, decided once)
@@ -1128,7 +1195,7 @@ struct BwdCall : RasterState {
 // The side structs and every argument check, in the order callers see their errors.  With P == 0 it ends after the
 // checks an empty scene needs (as check_common does).
 static int bwd_check_args(BwdCall &c, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
-                          const gsr_features_ext *feat) {
+                          const gsr_features_ext *feat, const gsr_distortion_ext *dist) {
     const gsr_backward_args *a = c.a;
     int rc = read_composite_ext(ext, a->background, c.e);
     if (rc) return rc;
@@ -1140,6 +1207,13 @@ static int bwd_check_args(BwdCall &c, const gsr_composite_ext *ext, const gsr_ab
     if (c.fx.given && a->stages != GSR_BWD_ALL)
         return fail(GSR_ERR_UNSUPPORTED, "features with a split backward (stages != GSR_BWD_ALL) are not built yet");
     c.feat_bwd = c.fx.given && c.fx.dL_dout_features != nullptr;
+    rc = read_distortion_ext(dist, c.dx);
+    if (rc) return rc;
+    if (c.dx.given && c.ab.dL_dmeans2D_abs)
+        return fail(GSR_ERR_UNSUPPORTED, "distortion with gsr_absgrad_ext.dL_dmeans2D_abs is not built");
+    if (c.dx.given && a->stages != GSR_BWD_ALL)
+        return fail(GSR_ERR_UNSUPPORTED, "distortion with a split backward (stages != GSR_BWD_ALL) is not built");
+    c.dist_bwd = c.dx.given && c.dx.dL_dD != nullptr;
     if (c.ab.densify_abs && !a->densify_stats)
         return fail(GSR_ERR_ARG, "gsr_absgrad_ext.densify_abs needs densify_stats");
     if (c.ab.densify_abs && !c.ab.dL_dmeans2D_abs)
@@ -1256,6 +1330,21 @@ static int bwd_features(BwdCall &c) {
     return GSR_OK;
 }
 
+// The distortion walk adds its geometry terms and, as inverse-depth weight, its depth term into the rows (and marks
+// the live flags): big_reduce and the per-Gaussian stage then see rows that hold every term
+static int bwd_distortion(BwdCall &c) {
+    hipStream_t stream = c.stream;
+    DistBwdParams dp;
+    dp.src = replay_src(c);
+    dp.depth_key = c.g.depth_key;
+    dp.map = c.dx.map; dp.k0 = dist_k0(c.dx); dp.nearp = c.dx.nearp; dp.dscale = dist_dscale(c.dx);
+    dp.final_T = c.im.final_T; dp.tot_w = c.dx.tot_w; dp.tot_m = c.dx.tot_m; dp.dL_dD = c.dx.dL_dD;
+    dp.rows = c.sc.rows;
+    dp.live = c.src.live ? c.g.live : nullptr;
+    GSR_STAGE(ST_DIST_BWD, c.dbg, launch_dist_bwd(stream, dp));
+    return GSR_OK;
+}
+
 // The big Gaussians' rows (and abs rows), summed by a workgroup each
 static int bwd_big_reduce(BwdCall &c) {
     hipStream_t stream = c.stream;
@@ -1287,7 +1376,7 @@ static int bwd_gaussians(BwdCall &c) {
     pp.focal_y = a->H / (2.0f * a->tan_fovy);
     pp.scale_modifier = a->scale_modifier;
     pp.antialiasing = a->antialiasing;
-    pp.has_invdepth = a->dL_dinvdepth != nullptr;
+    pp.has_invdepth = a->dL_dinvdepth != nullptr || (c.dist_bwd && c.R > 0);  // (the distortion's depth term: rows[..][9])
     pp.means3D = a->means3D; pp.opacities = a->opacities; pp.scales = a->scales; pp.rotations = a->rotations;
     pp.cov3D_precomp = a->cov3D_precomp; pp.shs = (a->colors_precomp ? nullptr : a->shs);
     pp.view = a->viewmatrix; pp.proj = a->projmatrix; pp.campos = a->campos;
@@ -1351,12 +1440,18 @@ int gsr_backward_abs(const gsr_backward_args *a, const gsr_composite_ext *ext, c
 
 int gsr_backward_features(const gsr_backward_args *a, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
                           const gsr_features_ext *feat, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr) {
+    return gsr_backward_distortion(a, ext, absgrad, feat, nullptr, alloc, alloc_ctx, stream_ptr);
+}
+
+int gsr_backward_distortion(const gsr_backward_args *a, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
+                            const gsr_features_ext *feat, const gsr_distortion_ext *dist, gsr_alloc_fn alloc,
+                            void *alloc_ctx, void *stream_ptr) {
     if (!a || !alloc) return fail(GSR_ERR_ARG, "null argument");
     BwdCall c{};
     c.a = a; c.alloc = alloc; c.alloc_ctx = alloc_ctx;
     c.stream = (hipStream_t)stream_ptr; c.dbg = a->debug != 0;
     hipStream_t stream = c.stream;
-    int rc = bwd_check_args(c, ext, absgrad, feat);
+    int rc = bwd_check_args(c, ext, absgrad, feat, dist);
     if (rc) return rc;
     if (a->P == 0) {  // no Gaussian: the background's gradients with T_final = 1, the camera's empty sums
         if (!camera_grads(a) && !c.e.dL_dbackground && !c.e.dL_dbackground_image) return GSR_OK;
@@ -1372,6 +1467,7 @@ int gsr_backward_features(const gsr_backward_args *a, const gsr_composite_ext *e
         if (c.R > 0) {
             rc = bwd_composite(c);
             if (!rc && c.feat_bwd) rc = bwd_features(c);
+            if (!rc && c.dist_bwd) rc = bwd_distortion(c);
             if (!rc) rc = bwd_big_reduce(c);
             if (rc) return rc;
         }

@@ -106,47 +106,6 @@ void launch_feat_fwd(hipStream_t s, const FeatFwdParams &p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Transposing wave reduction of NV (16 or 32) per-lane values, a plainer relative of wave_reduce_pair_store: each
-// level halves the number of values a lane carries by exchanging one half with the partner lane across one lane bit
-// (bit 5: v_permlane32_swap, bit 4: v_permlane16_swap, bit 3: row_ror:8, bit 2: row_half_mirror -- whose partner
-// 7 - l also flips bits 0 and 1, which the last two levels sum over anyway -- bit 1: quad_perm [2,3,0,1]), and the
-// levels left over are plain DPP adds.  Value n's total over the 64 lanes lands in the lanes whose bits spell n
-// (n = b5 + 2 b4 + 4 b3 + 8 b2 [+ 16 b1]) and is stored to dst[n].  A fixed tree: bitwise reproducible.  Every lane
-// must be active.
-// ------------------------------------------------------------------------------------------------
-template <int NV>
-__device__ __forceinline__ void wave_reduce_store(const float *v, float *__restrict__ dst, int lane) {
-    static_assert(NV == 16 || NV == 32, "16 or 32 values");
-    float a[NV / 2], b[NV / 4], c[NV / 8], d[NV / 16];
-#pragma unroll
-    for (int i = 0; i < NV / 2; i++) a[i] = sum_swap32(v[2 * i], v[2 * i + 1]);
-#pragma unroll
-    for (int i = 0; i < NV / 4; i++) b[i] = sum_swap16(a[2 * i], a[2 * i + 1]);
-    const bool h3 = (lane & 8) != 0, h2 = (lane & 4) != 0, h1 = (lane & 2) != 0;
-#pragma unroll
-    for (int i = 0; i < NV / 8; i++) {
-        const float keep = h3 ? b[2 * i + 1] : b[2 * i], send = h3 ? b[2 * i] : b[2 * i + 1];
-        c[i] = dpp_xadd<0x128>(keep, send);  // row_ror:8 (= lane ^ 8)
-    }
-#pragma unroll
-    for (int i = 0; i < NV / 16; i++) {
-        const float keep = h2 ? c[2 * i + 1] : c[2 * i], send = h2 ? c[2 * i] : c[2 * i + 1];
-        d[i] = dpp_xadd<0x141>(keep, send);  // row_half_mirror
-    }
-    int n = ((lane >> 5) & 1) | ((lane >> 3) & 2) | ((lane >> 1) & 4) | ((lane << 1) & 8);
-    float e;
-    if constexpr (NV == 32) {
-        const float keep = h1 ? d[1] : d[0], send = h1 ? d[0] : d[1];
-        e = dpp_xadd<0x4E>(keep, send);  // quad_perm [2,3,0,1]
-        n |= (lane << 3) & 16;
-    } else {
-        e = dpp_add<0x4E>(d[0]);
-    }
-    e = dpp_add<0xB1>(e);  // quad_perm [1,0,3,2]
-    if ((lane & (NV == 32 ? 1 : 3)) == 0) dst[n] = e;
-}
-
-// ------------------------------------------------------------------------------------------------
 // Feature compositing backward: one wave per tile, one channel block per launch (launched after render_bwd and before
 // big_reduce).  The reverse walk of render_bwd: T recovered by T / (1 - alpha) from final_T, one scalar D per pixel from
 // 0.  Per contributing (pixel, instance): g = sum_c f_ic dL/dF_c, d = g - D, D <- D + alpha d, q = G d T, and the lane

@@ -340,6 +340,31 @@ struct FeatGatherParams {
 };
 void launch_feat_gather(hipStream_t s, const FeatGatherParams &p);
 
+// ---- depth distortion map (gsr_distortion.hip) ----
+enum DistMap : int { DIST_MAP_Z = 0, DIST_MAP_NDC = 1 };  // gsrast.h GSR_DISTORTION_Z / GSR_DISTORTION_NDC
+// out (H,W) = sum_i sum_j w_i w_j |t_i - t_j| over the colour forward's pairs, replayed from its recorded state, and
+// the per-pixel totals tot_w = sum_i w_i, tot_m = sum_i w_i t_i the backward starts from; all three fully written
+struct DistFwdParams {
+    ReplaySrc src;
+    const uint32_t *depth_key;  // P: float bits of the view depth (GeomState::depth_key)
+    int map;
+    float k0, nearp;            // DIST_MAP_NDC: t = k0 (1 - nearp / z), k0 = far / (far - near)
+    float *out, *tot_w, *tot_m;
+};
+void launch_dist_fwd(hipStream_t s, const DistFwdParams &p);
+// The distortion backward, after launch_render_bwd (and launch_feat_bwd) and before launch_big_reduce: adds its
+// geometry terms into rows[..][0..5] and its depth term, as inverse-depth weight, into rows[..][9]
+struct DistBwdParams {
+    ReplaySrc src;
+    const uint32_t *depth_key;
+    int map;
+    float k0, nearp, dscale;    // dscale = far near / (far - near): z^2 dt/dz of DIST_MAP_NDC
+    const float *final_T, *tot_w, *tot_m, *dL_dD;  // (H,W) each
+    float *rows;
+    uint8_t *live;  // as RenderBwdParams::live, or null
+};
+void launch_dist_bwd(hipStream_t s, const DistBwdParams &p);
+
 // ---- per-Gaussian contribution statistics (gsr_contrib.hip) ----
 // The colour forward replayed once more, forward only: per contributing (Gaussian, pixel) pair the value
 // v = [m(pix) *] alpha_i T_i; per instance the wave's count, sum and max of v go to the instance's 16-B row

@@ -192,6 +192,8 @@ class ViewGradReducer:
 
     Feature channels (``forward_raw(..., features=...)``) are not exchanged: ``backward_chunked`` raises
     NotImplementedError for a forward state that carries features, and the exchange has no block for their gradient.
+    A state that carries a distortion map (``forward_raw(..., distortion=...)``) is refused by ``backward_chunked``
+    the same way: its terms are added by the one-call backward only.
 
     mode="sharded" (and mode="auto" when the cost model picks it): ``grads`` and ``sh_views_gradient`` cover only this
     rank's shard ``self.shard`` = [g0, g1); the caller steps those rows of its parameters (padded to

@@ -19,6 +19,10 @@ backward, as gsplat does: the absolute screen-space gradient of AbsGS for densif
 rasterizer(..., features=f) / rasterize_gaussians(..., features=f) with f (P,C), 1 <= C <= 64, also return the feature
 image (C,H,W) = sum_i alpha_i T_i f[i] (no background) as the last output, differentiable with respect to f and,
 through alpha, to everything the colour is (gsr_forward_features / gsr_backward_features).
+GaussianRasterizer(settings, distortion="z" | "ndc") / rasterize_gaussians(..., distortion=...) also return the depth
+distortion map (1,H,W) = sum_i sum_j w_i w_j |t_i - t_j| of Mip-NeRF 360 (2DGS's distloss) as the last output, after
+the feature image: t the view depth ("z") or 2DGS's far / (far - near) (1 - near / z) ("ndc", distortion_near /
+distortion_far), differentiable through the weights and through t (gsr_forward_distortion / gsr_backward_distortion).
 Every computation runs in the HIP kernels on the tensors' device; the scratch state the backward needs
 (geometry/binning/image buffers) lives in uint8 tensors saved on the autograd context.
 """
@@ -131,6 +135,37 @@ class ForwardState(NamedTuple):
     features: Optional[torch.Tensor] = None  # the prepared (P,C) feature channels, when the forward was given any
 
 
+class DistortionState(NamedTuple):
+    """What a forward with a distortion map leaves for its backward: the map and its planes, and the per-pixel totals
+    (2,H,W) = (sum_i w_i, sum_i w_i t_i) the reverse walk takes its prefix sums from."""
+    map: str
+    near: float
+    far: float
+    totals: torch.Tensor
+
+
+class _DistortionForwardState(ForwardState):
+    """A ForwardState that also carries a DistortionState as .distortion -- an attribute, not a field: the fields of
+    ForwardState, their count and their order are what earlier callers construct and index."""
+    distortion: Optional[DistortionState] = None
+
+
+def _distortion(distortion, near, far):
+    """(map name, near, far) of a distortion request, or None for None; RuntimeError for an unknown map, and for planes
+    that are not 0 < near < far ("ndc" needs both; "z" reads neither, but refuses bad ones)."""
+    if distortion is None:
+        return None
+    if distortion not in _native.DISTORTION_MAPS:
+        raise RuntimeError(f"distortion must be one of {sorted(_native.DISTORTION_MAPS)} or None, got {distortion!r}")
+    if distortion == "ndc" and (near is None or far is None):
+        raise RuntimeError("distortion='ndc' needs distortion_near and distortion_far")
+    near = 0.0 if near is None else float(near)
+    far = 0.0 if far is None else float(far)
+    if (distortion == "ndc" or near or far) and not (0.0 < near < far < float("inf")):
+        raise RuntimeError(f"distortion needs 0 < distortion_near < distortion_far, got near={near}, far={far}")
+    return distortion, near, far
+
+
 def _background(bg, H: int, W: int) -> bool:
     """Whether a background tensor is a per-pixel (3,H,W) image (True) or the (3,) vector; RuntimeError otherwise."""
     if bg is not None and tuple(bg.shape) == (3,):
@@ -156,7 +191,7 @@ def _features(features, P: int, device):
 
 
 def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                return_alpha=False, features=None):
+                return_alpha=False, features=None, distortion=None, distortion_near=None, distortion_far=None):
     """One call of gsr_forward.  Returns (color (3,H,W), radii (P,), invdepth (1,H,W), ForwardState).
     raster_settings.bg is the (3,) background or a (3,H,W) image, one background per pixel.  return_alpha=True returns
     (color, radii, invdepth, alpha (1,H,W), ForwardState), alpha = 1 - the transmittance left behind the pixel's last
@@ -165,7 +200,13 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
     composite writes where no Gaussian reaches, the background; every P > 0 colour is bitwise the same in both.
     features (P,C), 1 <= C <= 64: the feature image (C,H,W) = sum_i alpha_i T_i features[i], with the colour's weights
     and no background, is returned after alpha and before the state, which keeps the prepared features for the
-    backward (gsr_forward_features).  Colour, radii, invdepth and alpha are bitwise those of the call without."""
+    backward (gsr_forward_features).  Colour, radii, invdepth and alpha are bitwise those of the call without.
+    distortion "z" or "ndc": the depth distortion map (1,H,W) = sum_i sum_j w_i w_j |t_i - t_j| over each pixel's
+    contributors, with the colour's weights and no background term (exactly 0 where no Gaussian reaches), is returned
+    last before the state, after the feature image; t is the view depth ("z") or far / (far - near) (1 - near / z)
+    ("ndc": distortion_near, distortion_far, 0 < near < far).  The state then carries .distortion, a DistortionState
+    (gsr_forward_distortion); every other output keeps its bits."""
+    dist_spec = _distortion(distortion, distortion_near, distortion_far)
     lib = _native.load()
     device = means3D.device
     if device.type != "cuda":
@@ -202,6 +243,13 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
     if feat_c is not None:
         feat_image = torch.empty(feat_c.shape[1], H, W, dtype=torch.float32, device=device)
         feat = _native.FeaturesExt(C=int(feat_c.shape[1]), features=_ptr(feat_c), out_features=feat_image.data_ptr())
+    dist_image = dist = totals = None
+    if dist_spec is not None:
+        dist_image = torch.empty(1, H, W, dtype=torch.float32, device=device)
+        totals = torch.empty(2, H, W, dtype=torch.float32, device=device)
+        dist = _native.DistortionExt(map=_native.DISTORTION_MAPS[dist_spec[0]], near_plane=dist_spec[1],
+                                     far_plane=dist_spec[2], out_distortion=dist_image.data_ptr(),
+                                     total_weight=totals[0].data_ptr(), total_moment=totals[1].data_ptr())
     bufs = _Buffers(device)
     a = _native.ForwardArgs(
         P=P, D=int(rs.sh_degree), M=M, W=W, H=H, background=None if bg_image else _ptr(bg), means3D=_ptr(means3D_c),
@@ -213,13 +261,17 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
         out_invdepth=invdepth.data_ptr(), radii=radii.data_ptr())
     num_rendered = ctypes.c_int64(0)
     with torch.cuda.device(device):  # the library also switches to its stream's device (gsr_api.hip)
-        rc = _native.call_forward(lib, a, ext, feat, bufs.callback, _stream_handle(device), num_rendered)
+        rc = _native.call_forward(lib, a, ext, feat, bufs.callback, _stream_handle(device), num_rendered, dist=dist)
     bufs.raise_pending()
     _native.check(rc, "rasterize_gaussians")
     state = ForwardState(means3D_c, sh_c, col_c, op_c, sc_c, rot_c, cov_c, radii, bg, view, proj, campos,
                          bufs.get(_native.GSR_BUF_GEOM), bufs.get(_native.GSR_BUF_BINNING),
                          bufs.get(_native.GSR_BUF_IMAGE), int(num_rendered.value), int(a.num_big_out), M, feat_c)
     res = (color, radii, invdepth) + ((alpha,) if return_alpha else ()) + ((feat_image,) if feat is not None else ())
+    if dist is not None:
+        state = _DistortionForwardState(*state)
+        state.distortion = DistortionState(*dist_spec, totals)
+        res += (dist_image,)
     return (*res, state)
 
 
@@ -229,13 +281,16 @@ class _Upstream(NamedTuple):
     depth: Optional[torch.Tensor]
     alpha: Optional[torch.Tensor]
     features: Optional[torch.Tensor]
+    distortion: Optional[torch.Tensor]
     bg_image: bool                         # the forward's background is a (3,H,W) image
     ext: Optional[_native.CompositeExt]    # the backward's gsr_composite_ext, None for the plain call
 
 
-def _upstream(st: ForwardState, rs, grad_color, grad_depth, grad_alpha=None, grad_features=None, dbg=None):
+def _upstream(st: ForwardState, rs, grad_color, grad_depth, grad_alpha=None, grad_features=None, dbg=None,
+              grad_distortion=None):
     """The upstream gradients of colour (zeros when None), inverse depth, alpha ((1,H,W) or (H,W)) and the feature image
-    ((C,H,W), only for a state with features), checked and made contiguous float32, and the call's CompositeExt: given
+    ((C,H,W), only for a state with features) and the distortion map ((1,H,W) or (H,W), only for a state with
+    distortion), checked and made contiguous float32, and the call's CompositeExt: given
     with a background image, an alpha gradient or dbg, the destination of the background's gradient."""
     H, W = int(rs.image_height), int(rs.image_width)
     if grad_color is None:
@@ -254,13 +309,19 @@ def _upstream(st: ForwardState, rs, grad_color, grad_depth, grad_alpha=None, gra
         if tuple(grad_features.shape) != (C, H, W):
             raise RuntimeError(f"grad_out_features must have shape ({C}, {H}, {W}), got {tuple(grad_features.shape)}")
         grad_features = grad_features.to(torch.float32).contiguous()
+    if grad_distortion is not None:
+        if getattr(st, "distortion", None) is None:
+            raise RuntimeError("grad_out_distortion needs a state from forward_raw(..., distortion=...)")
+        if grad_distortion.numel() != H * W or grad_distortion.ndim not in (2, 3):
+            raise RuntimeError(f"grad_out_distortion must have shape (1, {H}, {W}), got {tuple(grad_distortion.shape)}")
+        grad_distortion = grad_distortion.to(torch.float32).contiguous()
     bg_image = _background(st.bg, H, W)
     ext = None
     if bg_image or grad_alpha is not None or dbg is not None:
         ext = _native.CompositeExt(background_image=_ptr(st.bg) if bg_image else None, dL_dalpha=_ptr(grad_alpha),
                                    dL_dbackground=None if bg_image else _ptr(dbg),
                                    dL_dbackground_image=_ptr(dbg) if bg_image else None)
-    return _Upstream(grad_color, grad_depth, grad_alpha, grad_features, bg_image, ext)
+    return _Upstream(grad_color, grad_depth, grad_alpha, grad_features, grad_distortion, bg_image, ext)
 
 
 def _backward_args(st: ForwardState, rs, up: _Upstream, accumulate_stats, **fields):
@@ -287,7 +348,8 @@ def _absgrad_ext(dabs: torch.Tensor, abs_stats, n: int):
 
 def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_depth=None, out=None,
                  compact_sh=False, accumulate_stats=False, camera_grads=False, grad_out_alpha=None,
-                 background_grad=False, absgrad=False, abs_stats=False, grad_out_features=None):
+                 background_grad=False, absgrad=False, abs_stats=False, grad_out_features=None,
+                 grad_out_distortion=None):
     """One call of gsr_backward.  Returns a dict of gradients (means3D, means2D, shs, colors_precomp,
     opacities, scales, rotations, cov3D_precomp); entries are None where the input was absent.
     `out` may supply preallocated contiguous float32 destinations (e.g. views into one flat buffer that is
@@ -319,7 +381,12 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     alpha it also enters every other gradient of the call, which then is the joint gradient of colour, inverse depth,
     alpha and features.  With grad_out_features=None "features" is zeros and every other gradient has the bits of the
     call without features.  The call is then gsr_backward_features; absgrad / abs_stats with it raise
-    NotImplementedError (the absolute sums of a joint call are not built)."""
+    NotImplementedError (the absolute sums of a joint call are not built).
+    grad_out_distortion (1,H,W) or (H,W), for a state that carries distortion (forward_raw(..., distortion=...)), is
+    the upstream gradient of the distortion map: through the weights and through the Gaussians' depths it enters every
+    other gradient of the call, the camera's included, in a fixed summation order.  With grad_out_distortion=None
+    every gradient has the bits of the call without distortion.  The call is then gsr_backward_distortion; absgrad /
+    abs_stats with it raise NotImplementedError."""
     if abs_stats and "densify_stats" not in (out or {}):
         raise RuntimeError("abs_stats=True needs out['densify_stats']")
     lib = _native.load()
@@ -359,14 +426,21 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     dproj = dst("projmatrix", 4, 4) if camera_grads else None
     dcampos = dst("campos", 3) if camera_grads else None
     dbg = dst("bg", *st.bg.shape) if (background_grad or "bg" in out) else None
-    up = _upstream(st, rs, grad_out_color, grad_out_depth, grad_out_alpha, grad_out_features, dbg)
+    up = _upstream(st, rs, grad_out_color, grad_out_depth, grad_out_alpha, grad_out_features, dbg,
+                   grad_out_distortion)
     feat = dfeat = None
     if st.features is not None:
         C = int(st.features.shape[1])
         dfeat = dst("features", P, C)
         feat = _native.FeaturesExt(C=C, features=_ptr(st.features), dL_dout_features=_ptr(up.features),
                                    dL_dfeatures=_ptr(dfeat))
-    # (features with absgrad: refused by the library, GSR_ERR_UNSUPPORTED -> NotImplementedError)
+    dist = None
+    ds = getattr(st, "distortion", None)
+    if ds is not None:
+        dist = _native.DistortionExt(map=_native.DISTORTION_MAPS[ds.map], near_plane=ds.near, far_plane=ds.far,
+                                     total_weight=ds.totals[0].data_ptr(), total_moment=ds.totals[1].data_ptr(),
+                                     dL_ddistortion=_ptr(up.distortion))
+    # (features or distortion with absgrad: refused by the library, GSR_ERR_UNSUPPORTED -> NotImplementedError)
     ab = None if dabs is None else _absgrad_ext(dabs, abs_stats, P)
     bufs = _Buffers(device)
     a = _backward_args(
@@ -379,7 +453,7 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
         dL_dviewmatrix=_ptr(dview), dL_dprojmatrix=_ptr(dproj), dL_dcampos=_ptr(dcampos))
     with torch.cuda.device(device):
         rc = _native.call_backward(lib, a, ext=up.ext, absgrad=ab, feat=feat, cb=bufs.callback,
-                                   stream=_stream_handle(device))
+                                   stream=_stream_handle(device), dist=dist)
     bufs.raise_pending()
     _native.check(rc, "rasterize_gaussians_backward")
     camera = dict(viewmatrix=dview, projmatrix=dproj, campos=dcampos) if camera_grads else {}
@@ -487,10 +561,14 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
     A chunk's out may hold means2D_abs ((g_end - g_begin), 2), backward_raw's "means2D_abs" for those Gaussians: then
     every chunk must, since the compositing call produces the rows they are summed from.  abs_stats=True forms each
     chunk's densify_stats[:, 0] from it (every chunk then needs both).
-    A state that carries features raises NotImplementedError: the split backward of feature channels is not built."""
+    A state that carries features raises NotImplementedError: the split backward of feature channels is not built;
+    so does a state that carries distortion."""
     lib = _native.load()
     rs = raster_settings
     st = state
+    if getattr(st, "distortion", None) is not None:
+        raise NotImplementedError("backward_chunked: a forward state with distortion needs backward_raw (the split "
+                                  "backward of the distortion map is not built)")
     if st.features is not None:
         raise NotImplementedError("backward_chunked: a forward state with features needs backward_raw (the split "
                                   "backward of feature channels is not built)")
@@ -579,8 +657,11 @@ def _campos_rows(spec):
 
 def _save_state(ctx, st: ForwardState):
     """Keep a ForwardState on an autograd context: its tensors saved (an empty one in place of None), the rest plain."""
-    tensors = st[:15] + (() if st.features is None else (st.features,))
+    ds = getattr(st, "distortion", None)
+    tensors = st[:15] + (() if st.features is None else (st.features,)) + (() if ds is None else (ds.totals,))
     ctx.meta = (st.num_rendered, st.num_big, st.M)
+    ctx.has_features = st.features is not None
+    ctx.distortion = None if ds is None else tuple(ds[:3])
     ctx.present = tuple(t is not None for t in tensors)
     empty = torch.empty(0, device=st.radii.device)
     ctx.save_for_backward(*[(t if t is not None else empty) for t in tensors])
@@ -588,19 +669,27 @@ def _save_state(ctx, st: ForwardState):
 
 def _saved_state(ctx) -> ForwardState:
     tensors = [t if present else None for t, present in zip(ctx.saved_tensors, ctx.present)]
-    return ForwardState(*tensors[:15], *ctx.meta, *tensors[15:])
+    extra = tensors[15:]
+    features = extra.pop(0) if ctx.has_features else None
+    if ctx.distortion is None:
+        return ForwardState(*tensors[:15], *ctx.meta, features)
+    st = _DistortionForwardState(*tensors[:15], *ctx.meta, features)
+    st.distortion = DistortionState(*ctx.distortion, extra.pop(0))
+    return st
 
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, flags=(False, False), features=None, bg=None, *camera):
-        # flags: (return_alpha, absgrad).  features: None or the (P,C) channels.  bg: None or the settings' bg once
+        # flags: (return_alpha, absgrad[, distortion: None or (map, near, far)]).  features: None or the (P,C) channels.  bg: None or the settings' bg once
         # more, camera: () or the settings' (viewmatrix, projmatrix, campos) once more, as inputs autograd can hand a
         # gradient to (rasterize_gaussians); the values are read from the settings either way
-        return_alpha, absgrad = flags
+        return_alpha, absgrad = flags[:2]
+        dmap, dnear, dfar = (flags[2] if len(flags) > 2 and flags[2] is not None else (None, None, None))
         res = forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                          return_alpha=return_alpha, features=features)
+                          return_alpha=return_alpha, features=features, distortion=dmap, distortion_near=dnear,
+                          distortion_far=dfar)
         ctx.raster_settings = raster_settings
         ctx.return_alpha = bool(return_alpha)
         # absgrad: the backward sets means2D.absgrad on the caller's tensor (as gsplat's does)
@@ -609,7 +698,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.camera = [(tuple(t.shape), t.device) for t in camera]
         _save_state(ctx, res[-1])
         ctx.set_materialize_grads(False)
-        return res[:-1]  # (color, radii, invdepth[, alpha][, feature_image])
+        return res[:-1]  # (color, radii, invdepth[, alpha][, feature_image][, distortion])
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, *rest):
@@ -617,10 +706,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         rest = list(rest)
         grad_out_alpha = rest.pop(0) if ctx.return_alpha else None
         grad_out_features = rest.pop(0) if st.features is not None else None
+        grad_out_distortion = rest.pop(0) if getattr(st, "distortion", None) is not None else None
         need = ctx.needs_input_grad
         g = backward_raw(st, ctx.raster_settings, grad_out_color, grad_out_depth, camera_grads=any(need[12:]),
                          grad_out_alpha=grad_out_alpha, background_grad=need[11], absgrad=ctx.absgrad_of is not None,
-                         grad_out_features=grad_out_features)
+                         grad_out_features=grad_out_features, grad_out_distortion=grad_out_distortion)
         if ctx.absgrad_of is not None:  # (P,3) with z = 0, so code that takes [:, :2] of means2D.grad works on it
             m2a = g["means2D_abs"]
             ctx.absgrad_of.absgrad = torch.cat([m2a, m2a.new_zeros(m2a.shape[0], 1)], dim=1)
@@ -641,7 +731,8 @@ class _RasterizeGaussians(torch.autograd.Function):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, return_alpha=False, absgrad=False, features=None):
+                        raster_settings, return_alpha=False, absgrad=False, features=None, distortion=None,
+                        distortion_near=None, distortion_far=None):
     """Differentiable with respect to the Gaussians' tensors and, where raster_settings.viewmatrix, .projmatrix or
     .campos requires grad, to those three as independent inputs (projmatrix being the full view-projection product:
     a caller optimising a pose builds projmatrix and campos from its view matrix in torch, which chains the three).
@@ -656,9 +747,15 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     features (P,C), 1 <= C <= 64: the call returns (color, radii, invdepth[, alpha], feature_image (C,H,W)) with
     feature_image = sum_i alpha_i T_i features[i] -- the colour's weights, no background.  It takes part in autograd:
     features.grad is populated, and a loss on it reaches means3D, opacities, scales, rotations and the camera through
-    alpha.  With absgrad=True it raises NotImplementedError (the absolute sums of a joint call are not built)."""
+    alpha.  With absgrad=True it raises NotImplementedError (the absolute sums of a joint call are not built).
+    distortion "z" or "ndc" (with distortion_near, distortion_far): the call's last output is the depth distortion map
+    (1,H,W) = sum_i sum_j w_i w_j |t_i - t_j| (forward_raw).  It takes part in autograd: a loss on it reaches means3D,
+    opacities, scales, rotations, means2D.grad and the camera.  With absgrad=True it raises NotImplementedError."""
     if features is not None and absgrad:
         raise NotImplementedError("features with absgrad=True are not built yet")
+    dist_spec = _distortion(distortion, distortion_near, distortion_far)
+    if dist_spec is not None and absgrad:
+        raise NotImplementedError("distortion with absgrad=True is not built")
     rs = raster_settings
     camera = (rs.viewmatrix, rs.projmatrix, rs.campos)
     if not (torch.is_grad_enabled() and all(torch.is_tensor(t) for t in camera)
@@ -666,8 +763,9 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         camera = ()  # the call as it is without camera gradients
     bg = rs.bg if (torch.is_grad_enabled() and torch.is_tensor(rs.bg) and rs.bg.requires_grad) else None
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, (bool(return_alpha), bool(absgrad)), features, bg,
-                                     *camera)
+                                     cov3Ds_precomp, raster_settings,
+                                     (bool(return_alpha), bool(absgrad)) + (() if dist_spec is None else (dist_spec,)),
+                                     features, bg, *camera)
 
 
 @torch.no_grad()
@@ -733,11 +831,14 @@ def mark_visible(positions: torch.Tensor, viewmatrix: torch.Tensor, projmatrix: 
 
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings, return_alpha: bool = False,
-                 absgrad: bool = False):
+                 absgrad: bool = False, distortion: Optional[str] = None, distortion_near: Optional[float] = None,
+                 distortion_far: Optional[float] = None):
         """return_alpha=True: the call returns (color, radii, invdepth, alpha (1,H,W)); with P == 0 its color is the
         background where the plain call's is zero (rasterize_gaussians).  absgrad=True: the backward sets
-        means2D.absgrad (rasterize_gaussians)."""
+        means2D.absgrad (rasterize_gaussians).  distortion="z" or "ndc" (with distortion_near, distortion_far): the
+        call's last output is the depth distortion map (1,H,W) (rasterize_gaussians)."""
         super().__init__()
+        self.distortion = _distortion(distortion, distortion_near, distortion_far)
         self.raster_settings = raster_settings
         self.return_alpha = bool(return_alpha)
         self.absgrad = bool(absgrad)
@@ -755,10 +856,11 @@ class GaussianRasterizer(nn.Module):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-        # (color, radii, invdepth[, alpha][, feature_image (C,H,W)]): rasterize_gaussians
+        # (color, radii, invdepth[, alpha][, feature_image (C,H,W)][, distortion (1,H,W)]): rasterize_gaussians
+        dmap, dnear, dfar = self.distortion or (None, None, None)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs, return_alpha=self.return_alpha, absgrad=self.absgrad,
-                                   features=features)
+                                   features=features, distortion=dmap, distortion_near=dnear, distortion_far=dfar)
 
     def contributions(self, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                       cov3D_precomp=None, pixel_weights=None, out=None, accumulate=False):

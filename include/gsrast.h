@@ -268,6 +268,51 @@ int gsr_forward_features(gsr_forward_args *args, const gsr_composite_ext *ext, c
 int gsr_backward_features(const gsr_backward_args *args, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
                           const gsr_features_ext *feat, gsr_alloc_fn alloc, void *alloc_ctx, void *stream);
 
+/* Depth distortion map: the Mip-NeRF 360 distortion loss per pixel (2DGS's and gsplat's distloss), a fourth side
+ * struct versioned by its own size, so every other struct and GSR_ABI_VERSION stay as they are.  Over the pairs the
+ * colour forward composited (sorted index below the pixel's contributor count, the composite's alpha decision; under
+ * the "guard" knob the guarded one), with the colour render's weights w_i = alpha_i T_i and a per-Gaussian depth t_i:
+ *   out_distortion(pix) = sum_i sum_j w_i w_j |t_i - t_j|    (no background term; exactly 0 where no Gaussian reaches)
+ *   map GSR_DISTORTION_Z:   t = z, the view-space depth whose inverse out_invdepth composites;
+ *   map GSR_DISTORTION_NDC: t = far / (far - near) * (1 - near / z), 2DGS's bounded mapping (near_plane, far_plane).
+ * Tile lists are sorted by view depth and both maps are non-decreasing in z, so it is evaluated in one pass as
+ * 2 sum_i w_i (t_i A_<i - M_<i) with the prefix sums A_<i = sum_(j<i) w_j and M_<i = sum_(j<i) w_j t_j.
+ *   forward: out_distortion, total_weight (sum_i w_i) and total_moment (sum_i w_i t_i), (H,W) each, fully written.  The
+ *     two totals are state: the backward needs them as the forward left them.  Every other output of the call keeps
+ *     the bits it has without the struct.
+ *   backward: dL_ddistortion (H,W) enters, through the weights and through t, EVERY gradient of the call (dL_dmeans2D /
+ *     dL_dopacity / dL_dmeans3D / dL_dcov3D / dL_dscales / dL_drotations, densify_stats, the camera gradients): its
+ *     geometry terms and its depth term are added into the per-instance gradient rows before the per-Gaussian stage, in
+ *     a fixed order (no float atomics): two calls give the same bits.  It needs no scratch beyond gsr_bwd_scratch_bytes
+ *     (or gsr_bwd_scratch_bytes_features with features).
+ *   dL_ddistortion == NULL: none of the distortion work is launched and every output keeps the bits it has without the
+ *     struct.
+ * With P = 0 or nothing rendered the three maps are zeros.  Together with gsr_features_ext in one call: supported, both
+ * add into the same rows, one launch after the other.
+ * GSR_ERR_ARG, before any device work or allocation: an unknown map; with GSR_DISTORTION_NDC near_plane <= 0 or
+ * far_plane <= near_plane (or either not a number); a missing out_distortion (forward) / total_weight / total_moment
+ * pointer; struct_size ending before the first pointer field.
+ * GSR_ERR_UNSUPPORTED, before any device work -- not built: distortion together with gsr_absgrad_ext.dL_dmeans2D_abs,
+ * and with stages != GSR_BWD_ALL (the split backward). */
+enum { GSR_DISTORTION_Z = 0, GSR_DISTORTION_NDC = 1 };
+typedef struct gsr_distortion_ext {
+    size_t struct_size;               /* sizeof as the caller was built; fields past it are read as NULL */
+    int map;                          /* GSR_DISTORTION_Z or GSR_DISTORTION_NDC */
+    float near_plane;                 /* GSR_DISTORTION_NDC: > 0 */
+    float far_plane;                  /* GSR_DISTORTION_NDC: > near_plane */
+    float *out_distortion;            /* forward: (H,W), fully written */
+    float *total_weight;              /* (H,W): written by the forward, read by the backward */
+    float *total_moment;              /* (H,W): written by the forward, read by the backward */
+    const float *dL_ddistortion;      /* backward: (H,W) or NULL */
+} gsr_distortion_ext;
+/* gsr_forward_features / gsr_backward_features are these with dist = NULL. */
+int gsr_forward_distortion(gsr_forward_args *args, const gsr_composite_ext *ext, const gsr_features_ext *feat,
+                           const gsr_distortion_ext *dist, gsr_alloc_fn alloc, void *alloc_ctx, void *stream,
+                           int64_t *num_rendered);
+int gsr_backward_distortion(const gsr_backward_args *args, const gsr_composite_ext *ext,
+                            const gsr_absgrad_ext *absgrad, const gsr_features_ext *feat,
+                            const gsr_distortion_ext *dist, gsr_alloc_fn alloc, void *alloc_ctx, void *stream);
+
 /* Per-Gaussian contribution statistics of one forward, for pruning and budgeting (LightGaussian's significance: the
  * sum; RadSplat: the max; Mini-Splatting / Taming-3DGS: the hit count; error-based densification: the sum under a
  * per-pixel error image).  Forward only: no gradient is involved.  GSR_ABI_VERSION and every other struct stay as they
