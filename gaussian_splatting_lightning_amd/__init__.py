@@ -6,6 +6,7 @@ include/gsrast.h and bound here with ctypes.  See DESIGN.md.
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, mark_visible,  # noqa: F401
                          rasterize_contributions, rasterize_gaussians)
+from .bilagrid import BilateralGrid, slice_image, total_variation_loss  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_contributions",
-           "mark_visible"]
+           "mark_visible", "BilateralGrid", "slice_image", "total_variation_loss"]

@@ -173,6 +173,8 @@ EXPORTED_SYMBOLS = (
     "gsr_forward_distortion", "gsr_backward_distortion",
     "gsr_contributions", "gsr_contrib_scratch_bytes", "gsr_densify_classify_keep",
     "gsr_mcmc_noise", "gsr_mcmc_relocation", "gsr_mcmc_apply",
+    "gsr_bilagrid_workspace_bytes", "gsr_bilagrid_slice_forward", "gsr_bilagrid_slice_backward",
+    "gsr_bilagrid_tv_num_partials", "gsr_bilagrid_tv_forward", "gsr_bilagrid_tv_backward",
 )
 
 _lib = None
@@ -245,6 +247,22 @@ def load(path: str | None = None):
         lib.gsr_mcmc_apply.argtypes = [ctypes.c_int64, ctypes.c_int64, _fp, _fp, _fp, ctypes.c_float, _fp,
                                        ctypes.POINTER(DensifyField), ctypes.c_int, ctypes.c_void_p]
         lib.gsr_mcmc_apply.restype = ctypes.c_int
+    if hasattr(lib, "gsr_bilagrid_slice_forward"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
+        i4, idx = [ctypes.c_int] * 4, ctypes.POINTER(ctypes.c_int32)  # idx: a host array
+        lib.gsr_bilagrid_workspace_bytes.argtypes = [ctypes.c_int] * 5
+        lib.gsr_bilagrid_workspace_bytes.restype = ctypes.c_size_t
+        lib.gsr_bilagrid_slice_forward.argtypes = [*i4, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, idx, _fp,
+                                                   ctypes.c_void_p]
+        lib.gsr_bilagrid_slice_forward.restype = ctypes.c_int
+        lib.gsr_bilagrid_slice_backward.argtypes = [*i4, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, idx, _fp,
+                                                    _fp, _fp, ctypes.c_void_p, ctypes.c_void_p]
+        lib.gsr_bilagrid_slice_backward.restype = ctypes.c_int
+        lib.gsr_bilagrid_tv_num_partials.argtypes = i4
+        lib.gsr_bilagrid_tv_num_partials.restype = ctypes.c_size_t
+        lib.gsr_bilagrid_tv_forward.argtypes = [*i4, _fp, _fp, ctypes.c_void_p]
+        lib.gsr_bilagrid_tv_forward.restype = ctypes.c_int
+        lib.gsr_bilagrid_tv_backward.argtypes = [*i4, _fp, _fp, _fp, ctypes.c_void_p]
+        lib.gsr_bilagrid_tv_backward.restype = ctypes.c_int
     lib.gsr_mark_visible.argtypes = [ctypes.c_int, _fp, _fp, _fp, _fp, ctypes.c_void_p]
     lib.gsr_mark_visible.restype = ctypes.c_int
     lib.gsr_sh_backward_views.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp,

@@ -2035,6 +2035,93 @@ int gsr_ssim_backward(int planes, int H, int W, const float *img1, const float *
     return GSR_OK;
 }
 
+// ---- bilateral grid (gsr_bilagrid.hip) ----
+static const char *bilagrid_grid_error(int num, int L, int Gh, int Gw) {
+    if (num <= 0 || L <= 0 || Gh <= 0 || Gw <= 0) return "bilagrid: num, L, Gh and Gw must be positive";
+    if ((double)num * 12 * L * Gh * Gw > 2147483647.0)
+        return "bilagrid: grid too large";
+    return nullptr;
+}
+
+static const char *bilagrid_shape_error(int num, int L, int Gh, int Gw, int B, int H, int W) {
+    if (const char *e = bilagrid_grid_error(num, L, Gh, Gw)) return e;
+    if (B <= 0 || H <= 0 || W <= 0) return "bilagrid: B, H and W must be positive";
+    if ((2 * (int64_t)std::max(H, W) + 1) * std::max(Gh, Gw) > 0x7fffffffLL || H > 16 * 65535 ||
+        (int64_t)H * W > 0x7fffffffLL)
+        return "bilagrid: image too large";
+    return nullptr;
+}
+
+static const char *bilagrid_index_error(int num, int B, const int32_t *grid_idx) {
+    if (!grid_idx) return "bilagrid: null argument";
+    for (int b = 0; b < B; b++)
+        if (grid_idx[b] < 0 || grid_idx[b] >= num) return "bilagrid: grid index outside [0, num)";
+    return nullptr;
+}
+
+size_t gsr_bilagrid_workspace_bytes(int L, int Gh, int Gw, int H, int W) {
+    if (bilagrid_shape_error(1, L, Gh, Gw, 1, H, W)) return 0;
+    return bilagrid_workspace_bytes(BgShape{L, Gh, Gw, H, W});
+}
+
+int gsr_bilagrid_slice_forward(int num, int L, int Gh, int Gw, const float *grids, int B, int H, int W,
+                               const float *image, const int32_t *grid_idx, float *out, void *stream_ptr) {
+    if (const char *e = bilagrid_shape_error(num, L, Gh, Gw, B, H, W)) return fail(GSR_ERR_ARG, e);
+    if (!grids || !image || !out) return fail(GSR_ERR_ARG, "bilagrid: null argument");
+    if (const char *e = bilagrid_index_error(num, B, grid_idx)) return fail(GSR_ERR_ARG, e);
+    hipStream_t s = (hipStream_t)stream_ptr;
+    StreamDeviceGuard device_guard(s);
+    launch_bilagrid_slice_forward(s, BgShape{L, Gh, Gw, H, W}, B, grid_idx, grids, image, out);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_bilagrid_slice_backward(int num, int L, int Gh, int Gw, const float *grids, int B, int H, int W,
+                                const float *image, const int32_t *grid_idx, const float *dL_dout, float *dL_dgrids,
+                                float *dL_dimage, void *workspace, void *stream_ptr) {
+    if (const char *e = bilagrid_shape_error(num, L, Gh, Gw, B, H, W)) return fail(GSR_ERR_ARG, e);
+    if (!grids || !image || !dL_dout) return fail(GSR_ERR_ARG, "bilagrid: null argument");
+    if (const char *e = bilagrid_index_error(num, B, grid_idx)) return fail(GSR_ERR_ARG, e);
+    const BgShape S{L, Gh, Gw, H, W};
+    if (dL_dgrids && !workspace && bilagrid_workspace_bytes(S) > 0)
+        return fail(GSR_ERR_ARG, "bilagrid: this shape needs gsr_bilagrid_workspace_bytes() of workspace");
+    if (!dL_dgrids && !dL_dimage) return GSR_OK;
+    hipStream_t s = (hipStream_t)stream_ptr;
+    StreamDeviceGuard device_guard(s);
+    if (dL_dimage) launch_bilagrid_slice_backward_image(s, S, B, grid_idx, grids, image, dL_dout, dL_dimage);
+    if (dL_dgrids)
+        GSR_HIP(launch_bilagrid_slice_backward_grid(s, S, num, B, grid_idx, image, dL_dout, dL_dgrids,
+                                                    (float *)workspace));
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+size_t gsr_bilagrid_tv_num_partials(int num, int L, int Gh, int Gw) {
+    return bilagrid_grid_error(num, L, Gh, Gw) ? 0 : bilagrid_tv_num_partials(num, L, Gh, Gw);
+}
+
+int gsr_bilagrid_tv_forward(int num, int L, int Gh, int Gw, const float *grids, float *partial_sums,
+                            void *stream_ptr) {
+    if (const char *e = bilagrid_grid_error(num, L, Gh, Gw)) return fail(GSR_ERR_ARG, e);
+    if (!grids || !partial_sums) return fail(GSR_ERR_ARG, "bilagrid: null argument");
+    hipStream_t s = (hipStream_t)stream_ptr;
+    StreamDeviceGuard device_guard(s);
+    launch_bilagrid_tv_forward(s, num, L, Gh, Gw, grids, partial_sums);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_bilagrid_tv_backward(int num, int L, int Gh, int Gw, const float *grids, const float *dL_dtv,
+                             float *dL_dgrids, void *stream_ptr) {
+    if (const char *e = bilagrid_grid_error(num, L, Gh, Gw)) return fail(GSR_ERR_ARG, e);
+    if (!grids || !dL_dtv || !dL_dgrids) return fail(GSR_ERR_ARG, "bilagrid: null argument");
+    hipStream_t s = (hipStream_t)stream_ptr;
+    StreamDeviceGuard device_guard(s);
+    launch_bilagrid_tv_backward(s, num, L, Gh, Gw, grids, dL_dtv, dL_dgrids);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
 int gsr_mark_visible(int P, const float *means3D, const float *viewmatrix, const float *projmatrix, uint8_t *present,
                      void *stream_ptr) {
     (void)projmatrix;

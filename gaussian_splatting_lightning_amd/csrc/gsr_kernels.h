@@ -562,4 +562,26 @@ void launch_ssim_backward(hipStream_t s, int planes, int H, int W, const float *
                           const float *dL_dmean, float inv_n, const float *d_mu1, const float *d_s11,
                           const float *d_s12, float *dL_dimg1);
 
+// ---- bilateral-grid colour correction (gsr_bilagrid.hip) ----
+constexpr int BG_MAX_BATCH = 8;  // images per slice launch
+struct BgShape {
+    int L, Gh, Gw, H, W;
+};
+struct BgBatch {
+    int b0;               // first image of the launch
+    int g[BG_MAX_BATCH];  // grid of image b0 + blockIdx.z
+};
+int bilagrid_splits(const BgShape &S);
+size_t bilagrid_workspace_bytes(const BgShape &S);
+void launch_bilagrid_slice_forward(hipStream_t s, const BgShape &S, int B, const int32_t *idx, const float *grids,
+                                   const float *image, float *out);
+void launch_bilagrid_slice_backward_image(hipStream_t s, const BgShape &S, int B, const int32_t *idx,
+                                          const float *grids, const float *image, const float *dout, float *dimage);
+hipError_t launch_bilagrid_slice_backward_grid(hipStream_t s, const BgShape &S, int num, int B, const int32_t *idx,
+                                               const float *image, const float *dout, float *dgrids, float *workspace);
+size_t bilagrid_tv_num_partials(int num, int L, int Gh, int Gw);
+void launch_bilagrid_tv_forward(hipStream_t s, int num, int L, int Gh, int Gw, const float *grids, float *partial);
+void launch_bilagrid_tv_backward(hipStream_t s, int num, int L, int Gh, int Gw, const float *grids,
+                                 const float *dL_dtv, float *dgrids);
+
 }  // namespace gsr

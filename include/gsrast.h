@@ -381,6 +381,37 @@ int gsr_ssim_backward(int planes, int H, int W, const float *img1, const float *
                       const float *dL_dmean, const float *dm_dmu1, const float *dm_dsigma1_sq,
                       const float *dm_dsigma12, float *dL_dimg1, void *stream);
 
+/* Bilateral-grid colour correction (Wang et al., "Bilateral Guided Radiance Field Processing", SIGGRAPH 2024; the
+ * layout of gsplat's lib_bilagrid).  grids is (num, 12, L, Gh, Gw) contiguous fp32 on the device: channel 4r + k of a
+ * grid multiplies input colour k (k = 3: the offset) into output colour r.  image, out and the gradients of both are
+ * (B, 3, H, W) contiguous fp32 on the device; grid_idx is a HOST array of B indices into [0, num): image b is sliced
+ * through grid grid_idx[b].  Pixel (y, x) with value v samples its grid trilinearly (border-clamped) at
+ *   ux = (x + 0.5) / W * (Gw - 1),  uy = (y + 0.5) / H * (Gh - 1),
+ *   uz = clamp((0.299 v0 + 0.587 v1 + 0.114 v2) * (L - 1), 0, L - 1)
+ * (a size-1 axis has coordinate 0) and out_r = A[4r] v0 + A[4r+1] v1 + A[4r+2] v2 + A[4r+3].
+ * Backward: dL_dgrids (num grids, written whole: exact zeros for a grid no image selects; images that share a grid are
+ * summed in image order; no atomics, so two calls give the same bits) and dL_dimage (through the affine, and through
+ * uz where 0 < gray < 1); either may be NULL to skip it, and with both NULL the call does nothing and is GSR_OK.
+ * dL_dgrids needs gsr_bilagrid_workspace_bytes(L, Gh, Gw, H, W) bytes of device workspace (one grid-sized slab per
+ * split of a lattice column's pixel support; 0 when the support is not split: workspace may then be NULL).
+ * Total variation: tv = (1 / num) sum over the three lattice axes of (the sum of squared first differences along the
+ * axis) / (12 (n - 1) (the other two sizes)), an axis of size 1 contributing 0.  The forward writes
+ * gsr_bilagrid_tv_num_partials() partial sums whose sum is tv; the backward writes dL_dgrids = dL_dtv[0] dtv/dgrids
+ * (dL_dtv: device scalar).
+ * GSR_ERR_ARG, before any device work: a NULL argument (other than the cases above), a non-positive num, L, Gh, Gw,
+ * B, H or W, a grid index outside [0, num), 12 num L Gh Gw, H W or (2 max(H, W) + 1) max(Gh, Gw) above 2^31 - 1, or H
+ * above 16 * 65535. */
+size_t gsr_bilagrid_workspace_bytes(int L, int Gh, int Gw, int H, int W);
+int gsr_bilagrid_slice_forward(int num, int L, int Gh, int Gw, const float *grids, int B, int H, int W,
+                               const float *image, const int32_t *grid_idx, float *out, void *stream);
+int gsr_bilagrid_slice_backward(int num, int L, int Gh, int Gw, const float *grids, int B, int H, int W,
+                                const float *image, const int32_t *grid_idx, const float *dL_dout, float *dL_dgrids,
+                                float *dL_dimage, void *workspace, void *stream);
+size_t gsr_bilagrid_tv_num_partials(int num, int L, int Gh, int Gw);
+int gsr_bilagrid_tv_forward(int num, int L, int Gh, int Gw, const float *grids, float *partial_sums, void *stream);
+int gsr_bilagrid_tv_backward(int num, int L, int Gh, int Gw, const float *grids, const float *dL_dtv,
+                             float *dL_dgrids, void *stream);
+
 /* Fused Adam step over up to 16 parameter groups in one launch -- replaces the torch.optim.Adam(eps=1e-15)
  * step of the reference's six Gaussian parameter groups (gs_lightning_module.py:114-134).  All arrays are
  * contiguous fp32 device arrays of n elements, updated in place; step is the 1-based step count of each
