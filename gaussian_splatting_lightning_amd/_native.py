@@ -175,6 +175,7 @@ EXPORTED_SYMBOLS = (
     "gsr_mcmc_noise", "gsr_mcmc_relocation", "gsr_mcmc_apply",
     "gsr_bilagrid_workspace_bytes", "gsr_bilagrid_slice_forward", "gsr_bilagrid_slice_backward",
     "gsr_bilagrid_tv_num_partials", "gsr_bilagrid_tv_forward", "gsr_bilagrid_tv_backward",
+    "gsr_mipfilter_rate", "gsr_activations_filter3d_forward", "gsr_activations_filter3d_backward",
 )
 
 _lib = None
@@ -263,6 +264,14 @@ def load(path: str | None = None):
         lib.gsr_bilagrid_tv_forward.restype = ctypes.c_int
         lib.gsr_bilagrid_tv_backward.argtypes = [*i4, _fp, _fp, _fp, ctypes.c_void_p]
         lib.gsr_bilagrid_tv_backward.restype = ctypes.c_int
+    if hasattr(lib, "gsr_mipfilter_rate"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
+        lib.gsr_mipfilter_rate.argtypes = [ctypes.c_int64, _fp, ctypes.c_int, _fp, ctypes.c_float, _fp, _fp, _fp,
+                                           ctypes.c_void_p]
+        lib.gsr_mipfilter_rate.restype = ctypes.c_int
+        lib.gsr_activations_filter3d_forward.argtypes = [ctypes.c_int64] + [_fp] * 7 + [ctypes.c_void_p]
+        lib.gsr_activations_filter3d_forward.restype = ctypes.c_int
+        lib.gsr_activations_filter3d_backward.argtypes = [ctypes.c_int64] + [_fp] * 10 + [ctypes.c_void_p]
+        lib.gsr_activations_filter3d_backward.restype = ctypes.c_int
     lib.gsr_mark_visible.argtypes = [ctypes.c_int, _fp, _fp, _fp, _fp, ctypes.c_void_p]
     lib.gsr_mark_visible.restype = ctypes.c_int
     lib.gsr_sh_backward_views.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp,

@@ -2122,6 +2122,69 @@ int gsr_bilagrid_tv_backward(int num, int L, int Gh, int Gw, const float *grids,
     return GSR_OK;
 }
 
+// ---- Mip-Splatting 3D smoothing filter (gsr_mipfilter.hip) ----
+int gsr_mipfilter_rate(int64_t P, const float *means3D, int V, const float *cameras, float near_plane, float *rate,
+                       float *zmin, int32_t *seen, void *stream_ptr) {
+    if (P < 0 || P > 0x7fffffffLL * 256) return fail(GSR_ERR_ARG, "mipfilter rate: bad P");
+    if (V < 1) return fail(GSR_ERR_ARG, "mipfilter rate: V must be at least 1");
+    if (!std::isfinite(near_plane)) return fail(GSR_ERR_ARG, "mipfilter rate: near must be finite");
+    if (!means3D || !cameras || !rate || !zmin || !seen) return fail(GSR_ERR_ARG, "mipfilter rate: null array");
+    if (((uintptr_t)cameras) & 63) return fail(GSR_ERR_ARG, "mipfilter rate: the camera table must be 64-B aligned");
+    if (P == 0) return GSR_OK;
+    MipRateArgs A{};
+    A.P = P;
+    A.V = V;
+    A.near = near_plane;
+    A.means3D = means3D;
+    A.cameras = reinterpret_cast<const MipCamera *>(cameras);
+    A.rate = rate; A.zmin = zmin; A.seen = seen;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_mipfilter_rate((hipStream_t)stream_ptr, A);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_activations_filter3d_forward(int64_t N, const float *scaling, const float *opacity, const float *rotation,
+                                     const float *filter_3D, float *scales, float *opacities, float *rotations,
+                                     void *stream_ptr) {
+    if (N < 0 || N > 0x7fffffffLL * 256) return fail(GSR_ERR_ARG, "filter3d activations: bad N");
+    if (!scaling || !opacity || !rotation || !filter_3D || !scales || !opacities || !rotations)
+        return fail(GSR_ERR_ARG, "filter3d activations: null array");
+    if (!aligned16(rotation) || !aligned16(rotations))
+        return fail(GSR_ERR_ARG, "filter3d activations: rotation arrays must be 16-B aligned");
+    if (N == 0) return GSR_OK;
+    Filter3DArgs A{};
+    A.N = N;
+    A.scaling = scaling; A.opacity = opacity; A.rotation = rotation; A.filter_3D = filter_3D;
+    A.scales = scales; A.opacities = opacities; A.rotations = rotations;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_activations_filter3d_forward((hipStream_t)stream_ptr, A);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_activations_filter3d_backward(int64_t N, const float *scaling, const float *opacity, const float *rotation,
+                                      const float *filter_3D, const float *dL_dscales, const float *dL_dopacities,
+                                      const float *dL_drotations, float *dL_dscaling, float *dL_dopacity,
+                                      float *dL_drotation, void *stream_ptr) {
+    if (N < 0 || N > 0x7fffffffLL * 256) return fail(GSR_ERR_ARG, "filter3d activations: bad N");
+    if (!scaling || !opacity || !rotation || !filter_3D || !dL_dscales || !dL_dopacities || !dL_drotations ||
+        !dL_dscaling || !dL_dopacity || !dL_drotation)
+        return fail(GSR_ERR_ARG, "filter3d activations: null array");
+    if (!aligned16(rotation) || !aligned16(dL_drotations) || !aligned16(dL_drotation))
+        return fail(GSR_ERR_ARG, "filter3d activations: rotation arrays must be 16-B aligned");
+    if (N == 0) return GSR_OK;
+    Filter3DArgs A{};
+    A.N = N;
+    A.scaling = scaling; A.opacity = opacity; A.rotation = rotation; A.filter_3D = filter_3D;
+    A.dL_dscales = dL_dscales; A.dL_dopacities = dL_dopacities; A.dL_drotations = dL_drotations;
+    A.dL_dscaling = dL_dscaling; A.dL_dopacity = dL_dopacity; A.dL_drotation = dL_drotation;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_activations_filter3d_backward((hipStream_t)stream_ptr, A);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
 int gsr_mark_visible(int P, const float *means3D, const float *viewmatrix, const float *projmatrix, uint8_t *present,
                      void *stream_ptr) {
     (void)projmatrix;

@@ -584,4 +584,35 @@ void launch_bilagrid_tv_forward(hipStream_t s, int num, int L, int Gh, int Gw, c
 void launch_bilagrid_tv_backward(hipStream_t s, int num, int L, int Gh, int Gw, const float *grids,
                                  const float *dL_dtv, float *dgrids);
 
+// ---- Mip-Splatting 3D smoothing filter: sampling rates and filtered activations (gsr_mipfilter.hip) ----
+struct MipCamera {       // one row of the (V,16) camera table, 64 B
+    float zc[4];         // viewmatrix[:, 2]: z = p . zc[:3] + zc[3]
+    float xc[4];         // viewmatrix[:, 0]
+    float yc[4];         // viewmatrix[:, 1]
+    float fx;            // W / (2 tanfovx)
+    float limx, limy;    // (1 + 2 margin) tanfovx, (1 + 2 margin) tanfovy
+    float pad;
+};
+static_assert(sizeof(MipCamera) == 64, "the camera table is (V,16) floats");
+struct MipRateArgs {
+    int64_t P;
+    int V;
+    float near;
+    const float *means3D;       // (P,3)
+    const MipCamera *cameras;   // (V)
+    float *rate, *zmin;         // (P)
+    int32_t *seen;              // (P)
+};
+void launch_mipfilter_rate(hipStream_t s, const MipRateArgs &A);
+
+struct Filter3DArgs {
+    int64_t N;
+    const float *scaling, *opacity, *rotation, *filter_3D;  // raw parameters (N,3) (N) (N,4), the filter (N)
+    float *scales, *opacities, *rotations;                  // forward outputs
+    const float *dL_dscales, *dL_dopacities, *dL_drotations;
+    float *dL_dscaling, *dL_dopacity, *dL_drotation;        // backward outputs
+};
+void launch_activations_filter3d_forward(hipStream_t s, const Filter3DArgs &A);
+void launch_activations_filter3d_backward(hipStream_t s, const Filter3DArgs &A);
+
 }  // namespace gsr

@@ -15,6 +15,9 @@ working: `_xyz`, `_features_dc`, `_features_rest`, `_opacity`, `_scaling`, `_rot
   per-Gaussian hit count / weight sum / weight max of GaussianRasterizer.contributions over a pass of views;
 * `inject_noise`, `relocate_dead`, `add_new` -- densify.py: 3DGS-MCMC's noise on the means, relocation of dead
   Gaussians and growth under a cap, one or two launches each;
+* `compute_3d_filter(cameras)`, `get_activated(filter_3d=True)`, `get_scaling_with_3D_filter`,
+  `get_opacity_with_3D_filter`, `save_ply(with_filter=True)`, `save_fused_ply` -- mipfilter.py: Mip-Splatting's 3D
+  smoothing filter as the `filter_3D` buffer and one fused launch for the filtered activations;
 * `reset_opacity`, `reset_max_radii2D`, `reset_xyz_gradient`, `step_sh_degree`, `ready_for_*`.
 
 `spatial_scale` is passed directly (the reference derives it from COLMAP cameras with pycolmap,
@@ -28,8 +31,11 @@ import torch
 from torch import nn
 
 from . import densify as _densify
+from . import mipfilter as _mip
 from . import ply as _ply
+from .activations import GaussianActivations
 from .knn import dist_cuda2
+from .mipfilter import FilteredGaussianActivations
 
 __all__ = ["GaussianModel", "rgb2sh0", "sh02rgb", "inverse_sigmoid", "C0"]
 
@@ -62,6 +68,7 @@ class GaussianModel(nn.Module):
         self.inversed_activation_opacity = inverse_sigmoid
         self.activation_scaling = torch.exp
         self.inversed_activation_scaling = torch.log
+        self.register_buffer("filter_3D", None)  # (N,1) once compute_3d_filter ran or a checkpoint brought it
         if colmap_ply is not None:
             self.initialize(colmap_ply)
         self.spatial_scale = spatial_scale
@@ -104,21 +111,70 @@ class GaussianModel(nn.Module):
             else:
                 self.register_buffer(k, torch.zeros(N, device=self.device))
         self.active_sh_degree = d["active_sh_degree"]
+        self.filter_3D = d.get("filter_3D")  # a Mip-Splatting checkpoint's column, else None
 
     def load_model_ply(self, ply_path: str) -> None:
         """gaussian_model.py:112-132 (its three loader bugs reproduced; see ply.load_ply)."""
         self._set_params(_ply.load_ply(ply_path, compat="gs_lightning", device=self.device))
 
     def load_ply(self, ply_path: str) -> None:
-        """The official 3DGS loader (third_party/.../gaussian_model.py:263-314)."""
+        """The official 3DGS loader (third_party/.../gaussian_model.py:263-314); a `filter_3D` property, when the file
+        has one, becomes the `filter_3D` buffer."""
         d = _ply.load_ply(ply_path, compat="official", device=self.device)
         self._set_params(d)
         self.max_sh_degree = max(self.max_sh_degree, d["active_sh_degree"])
 
-    def save_ply(self, ply_path: str) -> bool:
-        """gaussian_model.py:150-171."""
+    def save_ply(self, ply_path: str, with_filter: bool = False) -> bool:
+        """gaussian_model.py:150-171.  with_filter: also the `filter_3D` column of a Mip-Splatting checkpoint (the raw
+        parameters stay raw: such a file needs a loader that applies the filter, as load_ply + get_activated(True))."""
+        f = self._filter() if with_filter else None
         return _ply.save_ply(ply_path, self._xyz, self._features_dc, self._features_rest, self._opacity,
-                             self._scaling, self._rotation)
+                             self._scaling, self._rotation, filter_3D=f)
+
+    @torch.no_grad()
+    def save_fused_ply(self, ply_path: str) -> bool:
+        """A plain 3DGS checkpoint any viewer reads, the filter folded into the parameters: scale = log(s'), opacity =
+        logit(o')."""
+        f = self._filter()
+        scales, opacities, _ = _mip.activate_filtered(self._scaling.detach(), self._opacity.detach(),
+                                                      self._rotation.detach(), f)
+        return _ply.save_ply(ply_path, self._xyz, self._features_dc, self._features_rest,
+                             self.inversed_activation_opacity(opacities), self.inversed_activation_scaling(scales),
+                             self._rotation)
+
+    # ---- Mip-Splatting's 3D smoothing filter (mipfilter.py) ----
+    def compute_3d_filter(self, cameras, variance: float = 0.2, mode: str = "per_camera", near: float = 0.2,
+                          margin: float = 0.15) -> torch.Tensor:
+        """Recompute the `filter_3D` buffer (N,1) from the training cameras (mipfilter.compute_3d_filter).  Call it
+        again whenever the number of Gaussians changed (densify_and_prune, add_new, prune_by_contribution): the getters
+        below refuse a buffer of another length.  relocate_dead moves rows in place and keeps the length, so the moved
+        rows carry their destination's old values until the next recompute, as under upstream's schedule (every 100
+        steps and after each densification)."""
+        self.filter_3D = _mip.compute_3d_filter(self._xyz.detach(), cameras, variance=variance, mode=mode, near=near,
+                                                margin=margin)
+        return self.filter_3D
+
+    def _filter(self) -> torch.Tensor:
+        f, N = self.filter_3D, self._xyz.shape[0]
+        if f is None or f.shape[0] != N:
+            have = "no filter_3D" if f is None else f"a filter_3D of {f.shape[0]} rows"
+            raise RuntimeError(f"{have} for {N} Gaussians: call compute_3d_filter(cameras) first, and again after "
+                               "every change of their number")
+        return f
+
+    def get_activated(self, filter_3d: bool = False):
+        """(scales, opacities, rotations) from one fused launch (one more in the backward): the plain activations, or
+        with filter_3d=True the ones with the 3D smoothing filter folded in."""
+        if filter_3d:
+            f = self._filter()
+            return FilteredGaussianActivations.apply(self._scaling, self._opacity, self._rotation, f)
+        return GaussianActivations.apply(self._scaling, self._opacity, self._rotation)
+
+    def get_scaling_with_3D_filter(self) -> torch.Tensor:
+        return self.get_activated(filter_3d=True)[0]
+
+    def get_opacity_with_3D_filter(self) -> torch.Tensor:
+        return self.get_activated(filter_3d=True)[1]
 
     # ---- densification ----
     def update_max_radii2D(self, radii: torch.Tensor, visible_mask: torch.Tensor) -> None:

@@ -232,9 +232,12 @@ def load_ply(path: str, max_sh_degree: Optional[int] = None, compat: str = "offi
     out = dict(xyz=torch.empty((N, 3), **f32), features_dc=torch.empty((N, 1, 3), **f32),
                features_rest=torch.empty(rest_shape, **f32), opacity=torch.empty((N, 1), **f32),
                scaling=torch.empty((N, len(scale)), **f32), rotation=torch.empty((N, len(rot)), **f32))
-    _unpack(records, vert, big, [(out["xyz"], ["x", "y", "z"]), (out["features_dc"], dc),
-                                 (out["features_rest"], rest_cols), (out["opacity"], ["opacity"]),
-                                 (out["scaling"], scale), (out["rotation"], rot)])
+    plan = [(out["xyz"], ["x", "y", "z"]), (out["features_dc"], dc), (out["features_rest"], rest_cols),
+            (out["opacity"], ["opacity"]), (out["scaling"], scale), (out["rotation"], rot)]
+    if "filter_3D" in names:  # a Mip-Splatting checkpoint: the 3D smoothing filter's per-Gaussian size
+        out["filter_3D"] = torch.empty((N, 1), **f32)
+        plan.append((out["filter_3D"], ["filter_3D"]))
+    _unpack(records, vert, big, plan)
     out["active_sh_degree"] = active
     return out
 
@@ -252,8 +255,11 @@ def read_points_ply(path: str, device="cuda") -> Tuple[torch.Tensor, torch.Tenso
 
 @torch.no_grad()
 def save_ply(path: str, xyz: torch.Tensor, features_dc: torch.Tensor, features_rest: torch.Tensor,
-             opacity: torch.Tensor, scaling: torch.Tensor, rotation: torch.Tensor) -> bool:
-    """gaussian_model.py:150-171: binary little-endian float32 vertex records, normals zero."""
+             opacity: torch.Tensor, scaling: torch.Tensor, rotation: torch.Tensor,
+             filter_3D: Optional[torch.Tensor] = None) -> bool:
+    """gaussian_model.py:150-171: binary little-endian float32 vertex records, normals zero.  filter_3D (N) or (N,1),
+    when given, is appended as a `filter_3D` property after rot_*, where Mip-Splatting's checkpoints have it; without
+    it the file is the reference writer's."""
     dev = _device(xyz.device)
     N = int(xyz.shape[0])
     tens = [t.detach().to(dev, torch.float32).contiguous() for t in
@@ -261,6 +267,10 @@ def save_ply(path: str, xyz: torch.Tensor, features_dc: torch.Tensor, features_r
     xyz_, dc, rest, op, sc, rot = tens
     n_dc, n_rest = dc[0].numel() if N else dc.shape[1] * dc.shape[2], rest.shape[1] * rest.shape[2]
     names = attribute_names(n_dc, n_rest, sc.shape[1], rot.shape[1])
+    if filter_3D is not None:
+        if filter_3D.numel() != N:
+            raise ValueError(f"filter_3D holds {filter_3D.numel()} values for {N} Gaussians")
+        names.append("filter_3D")
     rb = 4 * len(names)
     pos = {n: 4 * i for i, n in enumerate(names)}
     Kd, Kr = dc.shape[1], rest.shape[1]
@@ -270,6 +280,8 @@ def save_ply(path: str, xyz: torch.Tensor, features_dc: torch.Tensor, features_r
             (rest, [f"f_rest_{c * Kr + k}" for k in range(Kr) for c in range(3)]),
             (op, ["opacity"]), (sc, [f"scale_{i}" for i in range(sc.shape[1])]),
             (rot, [f"rot_{i}" for i in range(rot.shape[1])])]
+    if filter_3D is not None:
+        plan.append((filter_3D.detach().to(dev, torch.float32).contiguous(), ["filter_3D"]))
     cols, fields, widths = [], [], []
     for t, cn in plan:
         if not cn:

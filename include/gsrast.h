@@ -561,6 +561,35 @@ enum { GSR_FIELD_OPACITY = 4 };
 int gsr_mcmc_apply(int64_t N, int64_t n, const int64_t *src_idx, const int64_t *dst_idx, const int32_t *occurrences,
                    float min_opacity, float *values, const gsr_densify_field *fields, int num_fields, void *stream);
 
+/* The 3D smoothing filter of Mip-Splatting (Yu et al., CVPR 2024).  Only functions are added: GSR_ABI_VERSION and every
+ * struct stay as they are.  All three return GSR_ERR_ARG before any device work on a NULL pointer or a negative count
+ * (the first also on V < 1 or a near_plane that is not finite), and launch nothing (GSR_OK) at P == 0 / N == 0.
+ *
+ * gsr_mipfilter_rate: per Gaussian i over the V cameras of `cameras`, a (V,16) fp32 device table, 64-B aligned, row k =
+ *     [ V_k[0..3][2] | V_k[0..3][0] | V_k[0..3][1] | fx_k, limx_k, limy_k, 0 ]
+ *   with V_k the row-vector view matrix (p_view = [p, 1] V_k), fx_k = W_k / (2 tanfovx_k), limx_k = (1 + 2 margin)
+ *   tanfovx_k and limy_k likewise: the view-space z = p . row[0..2] + row[3], x from row[4..7], y from row[8..11].
+ *   Camera k sees i when z > near_plane, |x| <= limx_k z and |y| <= limy_k z.  seen[i] = the number of cameras that see
+ *   i, rate[i] = the maximum of fx_k / z over them (0 when none does), zmin[i] = the minimum z (+inf when none does).
+ *   means3D (P,3); rate, zmin (P) fp32 and seen (P) int32 are written whole.  No atomics; two calls give the same bits.
+ *
+ * gsr_activations_filter3d_forward / _backward: the parameter activations (gsr_activations_forward) with the filter
+ *   folded in.  s = exp(scaling), o = sigmoid(opacity), f = filter_3D[i] >= 0 (N):
+ *     scales = sqrt(s^2 + f^2),  opacities = o prod_k (s_k / scales_k),  rotations = rotation / max(|rotation|, 1e-12),
+ *   so opacities prod scales = o prod s (the Gaussian's integral).  Where f == 0 the outputs are
+ *   gsr_activations_forward's bit for bit.  The backward takes the raw parameters and the filter again (not the
+ *   forward's outputs) and writes dL/d(raw) from dL/d(activated); filter_3D takes no gradient.  Shapes and alignment as
+ *   for gsr_activations_forward. */
+int gsr_mipfilter_rate(int64_t P, const float *means3D, int V, const float *cameras, float near_plane, float *rate,
+                       float *zmin, int32_t *seen, void *stream);
+int gsr_activations_filter3d_forward(int64_t N, const float *scaling, const float *opacity, const float *rotation,
+                                     const float *filter_3D, float *scales, float *opacities, float *rotations,
+                                     void *stream);
+int gsr_activations_filter3d_backward(int64_t N, const float *scaling, const float *opacity, const float *rotation,
+                                      const float *filter_3D, const float *dL_dscales, const float *dL_dopacities,
+                                      const float *dL_drotations, float *dL_dscaling, float *dL_dopacity,
+                                      float *dL_drotation, void *stream);
+
 /* PLY vertex records <-> parameter fields (the 3DGS checkpoint of gaussian_model.py:112-171 and
  * third_party/.../gaussian_model.py:239-314).  `records` are n fixed-size records of record_bytes each, on the
  * device; `columns` (host array, destination order: field after field, column after column) give each
