@@ -226,7 +226,10 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
             s_a[lane] = stage_rec_a(my_a);
             s_b[lane] = stage_rec_b(my_b);
             s_c[lane] = p.rec[gid].c;
-            s_m[lane] = cell_mask(p.strip_exact, my_a, my_b, row0, (float)(tx * BLOCK_X));
+            // bit 4: the instance needs the exponent-sign test (conic_is_definite cannot prove it)
+            const float col0 = (float)(tx * BLOCK_X);
+            const bool generic = !(p.definite_fast && conic_is_definite(my_a, my_b, col0, row0));
+            s_m[lane] = cell_mask(p.strip_exact, my_a, my_b, row0, col0) | (generic ? 16u : 0u);
         }
         __syncthreads();
         // strip k of instance j is live iff bit j of sk[k] (wave-uniform)
@@ -234,7 +237,10 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
         uint64_t sk[NP];
 #pragma unroll
         for (int k = 0; k < NP; k++) sk[k] = __ballot((mm >> (kbase + k)) & 1u);
-        auto pass = [&](const int j, float *m) -> bool {
+        // one choice of pass body per batch, as render_bwd_v5_kernel's
+        const bool definite = __ballot(mm & 16u) == 0;
+        auto pass = [&](auto definite_tag, const int j, float *m) -> bool {
+            constexpr bool DEFINITE = decltype(definite_tag)::value;
             const uint32_t idx = (uint32_t)(bend - 1 - j);
             const float4 a = s_a[j], b = s_b[j];  // a: x, y, A, B; b: C, o, r, g
             const float2 c = s_c[j];              // b, 1/depth
@@ -255,7 +261,8 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
                 const float power2 = power2_at(b.x, dy, P0, L);
                 const float G = __builtin_amdgcn_exp2f(power2);
                 const float alpha = fminf(0.99f, b.y * G);
-                if (!(idx < lastc[k] && !(power2 > 0.0f) && !(alpha < 1.0f / 255.0f))) continue;
+                // DEFINITE (every instance of the batch passes conic_is_definite): power2 <= 0 always
+                if (!(idx < lastc[k] && (DEFINITE || !(power2 > 0.0f)) && !(alpha < 1.0f / 255.0f))) continue;
                 any = true;
                 T[k] = T[k] * fast_rcp(1.f - alpha);
                 const float wgt = alpha * T[k];
@@ -291,13 +298,14 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
             }
             return any;
         };
-        for (int j = 0; j < cnt; j += 2) {
+        auto walk = [&](auto definite_tag, const int n) {  // instances [0, n) with one pass body
+        for (int j = 0; j < n; j += 2) {
             float m0[NM];
-            const bool any0 = pass(j, m0);
+            const bool any0 = pass(definite_tag, j, m0);
             float *dst = s_part[w][j];
-            if (j + 1 < cnt) {
+            if (j + 1 < n) {
                 float m1[NM];
-                const bool any1 = pass(j + 1, m1);
+                const bool any1 = pass(definite_tag, j + 1, m1);
                 if (__ballot(any0 || any1)) {
                     wave_reduce_pair_store<true, ABS>(m0, m1, dst, lane);
                 } else if (lane < NV) {
@@ -310,6 +318,12 @@ __global__ __launch_bounds__(64 * PARTS) void render_bwd_parts_kernel(RenderBwdP
                 dst[lane] = 0.f;
             }
         }
+        };
+        // two loops one after the other, one of them empty, as render_bwd_v5_kernel's
+        int dn = definite ? cnt : 0, gn = definite ? 0 : cnt;
+        asm("" : "+s"(dn), "+s"(gn));
+        walk(BoolTag<true>{}, dn);
+        walk(BoolTag<false>{}, gn);
         __syncthreads();
         if (w == 0 && lane < cnt) {
             float u[NV];
@@ -494,6 +508,7 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? (ABS ? GSR_BWD_SEG_ABS_MINW :
         const int cnt = min(BWD_BATCH, bend - (int)lo);
         float4 my_a = make_float4(0, 0, 0, 0), my_b = my_a;
         uint32_t my_row = 0, my_m = 0, my_gid = 0;
+        bool generic = false;  // this lane's instance needs the exponent-sign test (conic_is_definite cannot prove it)
         if (lane < cnt) {
             const uint32_t s_me = r0 + (uint32_t)(bend - 1 - lane);
             my_row = p.sorted_u[s_me];
@@ -506,7 +521,10 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? (ABS ? GSR_BWD_SEG_ABS_MINW :
             s_rec[lane].b = stage_rec_b(my_b);
             s_rec[lane].c = p.rec[gid].c;
             my_m = smask ? (uint32_t)p.strip_mask[s_me] : cell_mask(p.strip_exact, my_a, my_b, row0, col0);
+            if constexpr (!GUARD) generic = !(p.definite_fast && conic_is_definite(my_a, my_b, col0, row0));
         }
+        // one choice of pass body per batch, as the forward's (the guard keeps the generic body)
+        const bool definite = !GUARD && __ballot(generic) == 0;
         // sk[k] bit j: strip k of instance j (idx = bend - 1 - j) may hold a contributing pixel.  (Strip liveness and
         // compare skipping from the strips' n_contrib bounds measured 2.5 % slower -- SALU -- and was removed.)
         uint64_t sk[PIX_PER_LANE];
@@ -515,7 +533,8 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? (ABS ? GSR_BWD_SEG_ABS_MINW :
         wave_lds_sync();
         // one instance's pass over the lane's pixels: updates T / D, returns the lane's raw sums (Q0, Q1, Q2, w0..w3) and dx in m and the
         // ballot of the lanes that contributed
-        auto pass = [&](const int j, float *m) -> uint64_t {
+        auto pass = [&](auto definite_tag, const int j, float *m) -> uint64_t {
+            constexpr bool DEFINITE = decltype(definite_tag)::value;
             const uint32_t idx = (uint32_t)(bend - 1 - j);
             const FwdRec &r = s_rec[j];
             const float4 a = r.a, b = r.b;  // a: x, y, A, B; b: C, o, r, g
@@ -546,9 +565,14 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? (ABS ? GSR_BWD_SEG_ABS_MINW :
                 const float G = __builtin_amdgcn_exp2f(power2);
                 const float alpha = fminf(0.99f, b.y * G);
                 // the contributing lanes as a scalar mask straight from the compares: !(power2 > 0),
-                // !(alpha < 1/255) and idx < n_contrib
-                uint64_t ok = __builtin_amdgcn_fcmpf(power2, 0.0f, FCMP_ULE) &
-                              __builtin_amdgcn_fcmpf(alpha, GUARD ? GUARD_A_LO : 1.0f / 255.0f, FCMP_UGE);
+                // !(alpha < 1/255) and idx < n_contrib; DEFINITE (every instance of the batch passes
+                // conic_is_definite: power2 <= 0 always) without the first
+                uint64_t ok;
+                if constexpr (DEFINITE)
+                    ok = __builtin_amdgcn_fcmpf(alpha, 1.0f / 255.0f, FCMP_UGE);
+                else
+                    ok = __builtin_amdgcn_fcmpf(power2, 0.0f, FCMP_ULE) &
+                         __builtin_amdgcn_fcmpf(alpha, GUARD ? GUARD_A_LO : 1.0f / 255.0f, FCMP_UGE);
                 if constexpr (GUARD) {  // the forward's guarded alpha decision, taken by the same test (gsr_common.h)
                     const uint64_t near = ok & ~__builtin_amdgcn_fcmpf(alpha, GUARD_A_HI, FCMP_UGE);
                     if (__builtin_expect(near != 0, 0)) {  // rare
@@ -594,31 +618,20 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? (ABS ? GSR_BWD_SEG_ABS_MINW :
             }
             return any;
         };
+        // the instance loop with one pass body: over the set `un` (UNION), else over instances [0, n)
+        auto walk = [&](auto definite_tag, [[maybe_unused]] uint64_t un, [[maybe_unused]] const int n) {
         if constexpr (UNION) {
-        // pair up only the instances that reach a live strip (lowest first); an instance's gradient bits do not
-        // depend on its partner (wave_reduce_pair_store), and the others get zero sums from their own lane
-        uint64_t un = 0;
-#pragma unroll
-        for (int k = 0; k < PIX_PER_LANE; k++) un |= sk[k];
-        un &= cnt >= 64 ? ~0ull : (1ull << cnt) - 1ull;
-        if (lane < cnt && !((un >> lane) & 1ull)) {
-            float4 *z = reinterpret_cast<float4 *>(s_part[lane]);
-            z[0] = make_float4(0.f, 0.f, 0.f, 0.f);
-            z[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (ABS) z[2] = make_float4(0.f, 0.f, 0.f, 0.f);
-            else *reinterpret_cast<float2 *>(s_part[lane] + 8) = make_float2(0.f, 0.f);
-        }
         while (un) {
             const int j0 = (int)__builtin_ctzll(un);
             un &= ~(1ull << j0);  // s_andn2 with the strip tests' bit (un & (un - 1) costs three SALU)
             float m0[NM];
-            const uint64_t any0 = pass(j0, m0);
+            const uint64_t any0 = pass(definite_tag, j0, m0);
             float *dst = s_part[j0];
             if (un) {
                 const int j1 = (int)__builtin_ctzll(un);
                 un &= ~(1ull << j1);
                 float m1[NM];
-                const uint64_t any1 = pass(j1, m1);
+                const uint64_t any1 = pass(definite_tag, j1, m1);
                 float *dst1 = s_part[j1];
                 if (any0 | any1) {
                     wave_reduce_pair_store<true, ABS>(m0, m1, dst, lane, dst1);
@@ -633,13 +646,13 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? (ABS ? GSR_BWD_SEG_ABS_MINW :
             }
         }
         } else {
-        for (int j = 0; j < cnt; j += 2) {
+        for (int j = 0; j < n; j += 2) {
             float m0[NM];
-            const uint64_t any0 = pass(j, m0);
+            const uint64_t any0 = pass(definite_tag, j, m0);
             float *dst = s_part[j];
-            if (j + 1 < cnt) {
+            if (j + 1 < n) {
                 float m1[NM];
-                const uint64_t any1 = pass(j + 1, m1);
+                const uint64_t any1 = pass(definite_tag, j + 1, m1);
                 if (any0 | any1) {
                     wave_reduce_pair_store<true, ABS>(m0, m1, dst, lane);
                 } else if (lane < NV) {
@@ -652,6 +665,36 @@ __global__ __launch_bounds__(64, GUARD ? 4 : SEG ? (ABS ? GSR_BWD_SEG_ABS_MINW :
                 dst[lane] = 0.f;
             }
         }
+        }
+        };
+        uint64_t un = 0;
+        if constexpr (UNION) {
+            // pair up only the instances that reach a live strip (lowest first); an instance's gradient bits do not
+            // depend on its partner (wave_reduce_pair_store), and the others get zero sums from their own lane
+#pragma unroll
+            for (int k = 0; k < PIX_PER_LANE; k++) un |= sk[k];
+            un &= cnt >= 64 ? ~0ull : (1ull << cnt) - 1ull;
+            if (lane < cnt && !((un >> lane) & 1ull)) {
+                float4 *z = reinterpret_cast<float4 *>(s_part[lane]);
+                z[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+                z[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (ABS) z[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+                else *reinterpret_cast<float2 *>(s_part[lane] + 8) = make_float2(0.f, 0.f);
+            }
+        }
+        // The batch's body is chosen by handing the batch to one of two loops that run one after the other, the other
+        // loop getting nothing; set and count pass through an empty asm so that the compiler cannot turn the sequence
+        // back into the two arms of a branch (as arms, T, D and the gradients' inputs got a second set of registers
+        // with copies at every batch: 79 -> 88 VGPRs, 6 -> 5 waves in the form without the depth gradient).
+        if constexpr (GUARD) {
+            walk(BoolTag<false>{}, un, cnt);
+        } else {
+            uint64_t dset = definite ? un : 0ull, gset = definite ? 0ull : un;
+            int dn = definite ? cnt : 0, gn = definite ? 0 : cnt;
+            if constexpr (UNION) asm("" : "+s"(dset), "+s"(gset));
+            else asm("" : "+s"(dn), "+s"(gn));
+            walk(BoolTag<true>{}, dset, dn);
+            walk(BoolTag<false>{}, gset, gn);
         }
         wave_lds_sync();
         if (lane < cnt) {
@@ -751,6 +794,7 @@ bool launch_render_bwd(hipStream_t s, const RenderBwdParams &p) {
     if (p.num_tiles <= 0) return false;
     RenderBwdParams q = p;
     q.strip_exact = tuning(K_strip_exact);
+    q.definite_fast = tuning(K_definite_fast);
     q.stamps = tuning(K_stamp) ? stamp_buffer(1) : nullptr;
     const bool gd = tuning(K_guard) != 0;  // the segmented and whole-tile walks, not the parts form
     if (p.seg_list && p.ck_flag && p.ckpt && p.ctot && p.seg_count && p.num_tiles <= (int)SEG_MAX_TILES) {

@@ -631,7 +631,7 @@ __device__ __forceinline__ float select_mask(uint64_t mask, float a, float b) {
     return r;
 }
 // LLVM CmpInst predicates for __builtin_amdgcn_fcmpf / __builtin_amdgcn_uicmp
-constexpr int FCMP_OLT = 4, FCMP_OLE = 5, FCMP_UGE = 11, FCMP_ULE = 13, ICMP_ULT = 36;
+constexpr int FCMP_OGE = 3, FCMP_OLT = 4, FCMP_OLE = 5, FCMP_UGE = 11, FCMP_ULE = 13, ICMP_ULT = 36;
 
 // One staged compositing record in LDS (48 B): both composite passes read a batch's instances from an array
 // of these with immediate offsets from one address.
@@ -761,6 +761,41 @@ __device__ __forceinline__ uint32_t strip_mask_exact(float4 a, float4 b, float r
 
 __device__ __forceinline__ uint32_t cell_mask(bool exact, float4 a, float4 b, float row0, float col0) {
     return exact ? strip_mask_exact(a, b, row0, col0) : strip_mask(a, b, row0);
+}
+
+// Whether the compositing exponent of this raw record (a = x, y, conic a, conic b; b = conic c, opacity, ...) is
+// provably never positive and never NaN at any pixel of the tile at (col0, row0), and its o * exp2(power2) never NaN:
+// for a batch of such instances the composites run walk bodies without the `power2 <= 0` test (knob definite_fast,
+// DESIGN.md §5).  power2_at rounds P0 = (A' dx) dx twice, L = B' dx once, the inner fma once and the outer fma once, on
+// the staged (A', B', C') = -log2(e) (a/2, b, c/2), each rounded once.  The outer rounding is relative to the result
+// and cannot change its sign; with eps = 2^-24 the others, and the staging, move the value by at most
+//     3 eps (|A'| dx^2 + |B' dx dy| + |C'| dy^2) <= 12 eps lmax' r^2      (|b| <= sqrt(a c): |B' dx dy| <= |A'| dx^2 +
+// |C'| dy^2; a, c <= lmax; a factor 2 of slack), r^2 = dx^2 + dy^2 in the computed offsets, while the exact form is at
+// most -lmin' r^2.  So power2 <= 0 whenever lmin / lmax > 12 eps = 7.2e-7 (a CPU sweep in the kernel's operation
+// order, tests/test_definite_conic_host.py: positive exponents at ratios of 1e-7 and below, none at 1e-6).  The lmin
+// computed here is a cancelling difference with absolute error ~5 eps lmax = 3e-7 lmax, so lmin >= TAU lmax with
+// TAU = 1e-4 leaves a true ratio above 9.9e-5: 130 times the bound.  The other conditions keep every term where that
+// error model holds: lmax <= 2^10 and the centre within 2^15 px of the tile (no term above 2^42: no inf - inf),
+// lmin >= 2^-30 and |x|, |y| >= 2^-16 (a non-zero offset from an integer pixel is then >= 2^-41 and lmin' r^2 >=
+// 2^-113: no term of the bound is subnormal), and a finite opacity (o exp2(power2) is then a number, and
+// `o exp2(power2) >= 1/255` ordered is the decision `min(0.99, .) >= 1/255` unordered).  Every test is ordered, so a
+// NaN anywhere, det <= 0 and anything else this cannot prove stay with the generic body.  Uncontracted, so that the
+// numpy restatement of the tests computes the same bits.
+template <bool V>
+struct BoolTag {  // compile-time flag of the walk lambdas: walk(BoolTag<true>{}, ...) runs the DEFINITE body
+    static constexpr bool value = V;
+};
+constexpr float DEFINITE_TAU = 1e-4f;
+__device__ __forceinline__ bool conic_is_definite(float4 a, float4 b, float col0, float row0) {
+#pragma clang fp contract(off)
+    const float A = a.z, B = a.w, C = b.x;
+    const float det = A * C - B * B;
+    const float hd = 0.5f * (A - C), hs = 0.5f * (A + C);
+    const float rad = sqrtf(hd * hd + B * B);
+    const float lmin = hs - rad, lmax = hs + rad;
+    return A > 0.f && C > 0.f && det > 0.f && lmax <= 1024.f && lmin >= DEFINITE_TAU * lmax && lmin >= 0x1p-30f &&
+           fabsf(a.x - col0) <= 32768.f && fabsf(a.y - row0) <= 32768.f && fabsf(a.x) >= 0x1p-16f &&
+           fabsf(a.y) >= 0x1p-16f && fabsf(b.y) <= 3.0e38f;
 }
 
 // --- per-instance gradient rows (render_bwd -> big_reduce / preprocess_bwd) -------------------------

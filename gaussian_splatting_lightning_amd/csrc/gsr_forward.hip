@@ -658,6 +658,10 @@ template <int NPIX, int MIN_WAVES, bool CKPT = false, bool GUARD = false, bool S
 __global__ __launch_bounds__(256, MIN_WAVES) void render_fwd_v6_kernel(RenderFwdParams p) {
     constexpr int PARTS = 4 / NPIX;
     static_assert(!SMASK || PARTS == 1, "strip masks are recorded by whole-tile waves");
+    // Forms with the second walk body for batches of definite conics (conic_is_definite).  Not the guard's, which
+    // re-decides alpha with thresholds of its own, and not the whole-tile forms compiled for 6 and 4 waves per SIMD:
+    // the second loop's scalars took them from 98 to 106 SGPRs and from 8 to 7 resident waves.
+    constexpr bool FAST = !GUARD && !(NPIX == 4 && MIN_WAVES < 8);
     __shared__ FwdRec s_rec[4][64];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -717,6 +721,7 @@ __global__ __launch_bounds__(256, MIN_WAVES) void render_fwd_v6_kernel(RenderFwd
         if (CKPT && base > r0 && (base - r0) % p.ck_k == 0) store_ck(base - r0);
         const uint32_t s = base + lane;
         uint32_t m = 0;
+        bool generic = false;  // this lane's instance needs the exponent-sign test (conic_is_definite cannot prove it)
         if (s < r1) {
             const uint32_t u = p.sorted_u[s];
             const uint32_t gid = p.inst_gid[u];
@@ -728,7 +733,10 @@ __global__ __launch_bounds__(256, MIN_WAVES) void render_fwd_v6_kernel(RenderFwd
             sr[lane].c = p.rec[gid].c;
             if (GUARD) sr[lane].pad.x = __uint_as_float(gid);  // the guard's slow path reloads the raw record
             m = cell_mask(p.strip_exact, ga, gb, row0, col0) >> kbase;
+            if constexpr (FAST) generic = !(p.definite_fast && conic_is_definite(ga, gb, col0, row0));
         }
+        // one choice of walk body per batch (a per-instance choice between two hot bodies costs phi moves)
+        const bool definite = FAST && __ballot(generic) == 0;
         uint64_t sk[NPIX];
 #pragma unroll
         for (int k = 0; k < NPIX; k++) sk[k] = livek[k] ? __ballot((m >> k) & 1u) : 0ull;  // finished strips: none
@@ -743,7 +751,8 @@ __global__ __launch_bounds__(256, MIN_WAVES) void render_fwd_v6_kernel(RenderFwd
         uint64_t cb[NPIX];  // SMASK: bit j of cb[k] = some pixel of strip k took instance j
 #pragma unroll
         for (int k = 0; k < NPIX; k++) cb[k] = 0;
-        auto walk = [&](uint64_t &un) {
+        auto walk = [&](auto definite_tag, uint64_t &un) {
+        constexpr bool DEFINITE = decltype(definite_tag)::value;
         while (un) {
             const uint32_t j = (uint32_t)__builtin_ctzll(un);
             const uint64_t bit = 1ull << j;
@@ -758,14 +767,22 @@ __global__ __launch_bounds__(256, MIN_WAVES) void render_fwd_v6_kernel(RenderFwd
                 if (!(sk[k] & bit)) continue;  // wave-uniform
                 // dy = y - pixel row in one subtraction (the reference's own form): no per-instance row offset
                 const float power2 = power2_at(b.x, a.y - off[k], P0, L);
-                const float alpha = fminf(0.99f, b.y * __builtin_amdgcn_exp2f(power2));
+                const float ar = b.y * __builtin_amdgcn_exp2f(power2);
+                const float alpha = fminf(0.99f, ar);
                 const float test_T = T[k] * (1 - alpha);
                 // lane masks straight from the compares (scalar registers): ok = power2 <= 0 (ordered, so false
                 // for a retired pixel's NaN exponent; power2 is never NaN otherwise) and !(alpha < 1/255)
                 // GUARD: the alpha test at the band's lower edge, then the pairs inside the band re-decided (one
                 // extra compare per pair: outside the band alpha >= A_LO <=> alpha >= 1/255)
-                uint64_t ok = __builtin_amdgcn_fcmpf(power2, 0.0f, FCMP_OLE) &
-                              __builtin_amdgcn_fcmpf(alpha, GUARD ? GUARD_A_LO : 1.0f / 255.0f, FCMP_UGE);
+                // DEFINITE (every instance of the batch passes conic_is_definite: power2 <= 0 wherever it is a number):
+                // the one ordered test o exp2(power2) >= 1/255, the decision alpha >= 1/255 (0.99 > 1/255) and false
+                // for a retired pixel's NaN
+                uint64_t ok;
+                if constexpr (DEFINITE)
+                    ok = __builtin_amdgcn_fcmpf(ar, 1.0f / 255.0f, FCMP_OGE);
+                else
+                    ok = __builtin_amdgcn_fcmpf(power2, 0.0f, FCMP_OLE) &
+                         __builtin_amdgcn_fcmpf(alpha, GUARD ? GUARD_A_LO : 1.0f / 255.0f, FCMP_UGE);
                 const uint64_t low = __builtin_amdgcn_fcmpf(test_T, 0.0001f, FCMP_OLT);
                 if constexpr (GUARD) {  // alpha decisions near 1/255 from the oracle's arithmetic (gsr_common.h)
                     const uint64_t near = ok & ~__builtin_amdgcn_fcmpf(alpha, GUARD_A_HI, FCMP_UGE);
@@ -807,17 +824,29 @@ __global__ __launch_bounds__(256, MIN_WAVES) void render_fwd_v6_kernel(RenderFwd
             }
         }
         };
+        // The batch's body is chosen by handing the instance set to one of two loops that run one after the other, the
+        // other loop getting the empty set; the sets pass through an empty asm so that the compiler cannot turn the
+        // sequence back into the two arms of a branch.  As arms, the pixels' accumulators got a second set of registers
+        // with copies at every batch (the whole-tile form went from 58 to 79 VGPRs).
+        auto walk_set = [&](uint64_t set) {
+            if constexpr (!FAST) {
+                walk(BoolTag<false>{}, set);
+            } else {
+                uint64_t dset = definite ? set : 0ull, gset = definite ? 0ull : set;
+                asm("" : "+s"(dset), "+s"(gset));
+                walk(BoolTag<true>{}, dset);
+                walk(BoolTag<false>{}, gset);
+            }
+        };
         if (CKPT && p.ck_k == 32 && base + 32 < r1) {  // 32-instance checkpoints: one in the middle of the batch
-            uint64_t lo = un & 0xffffffffull;
-            walk(lo);
+            walk_set(un & 0xffffffffull);
             store_ck(base + 32 - r0);
             uint64_t live = 0;
 #pragma unroll
             for (int k = 0; k < NPIX; k++) live |= sk[k];
-            uint64_t hi = un & live & ~0xffffffffull;
-            walk(hi);
+            walk_set(un & live & ~0xffffffffull);
         } else {
-            walk(un);
+            walk_set(un);
         }
         contributor = cbase + min(64u, r1 - base);
         if (SMASK && s < r1) {
@@ -914,6 +943,7 @@ void launch_render_fwd(hipStream_t s, const RenderFwdParams &p0) {
     if (p0.num_tiles <= 0) return;
     RenderFwdParams p = p0;
     p.strip_exact = tuning(K_strip_exact);
+    p.definite_fast = tuning(K_definite_fast);
     p.stamps = tuning(K_stamp) ? stamp_buffer(0) : nullptr;
     const int parts = render_fwd_parts(p.num_tiles);
     if (parts != 1) p.xcd = 0;

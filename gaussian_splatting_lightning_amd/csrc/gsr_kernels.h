@@ -151,6 +151,7 @@ struct RenderFwdParams {
     uint32_t *n_contrib, *tile_last;
     uint4 *stamps; // diagnostics (set by launch), or null
     int strip_exact;  // strip skipping mask: 1 strip_mask_exact (column-band extent), 0 strip_mask (set by launch)
+    int definite_fast;  // batches of definite conics walk without the exponent-sign test (set by launch)
     // segmented-backward checkpoints (BinningState::ckpt, ImageState::ctot / ck_flag), or null: written every ck_k
     // instances when the launch runs tiles in 4 parts; *ck_flag = ck_k if it did, else 0
     float *ckpt = nullptr, *ctot = nullptr;
@@ -187,6 +188,7 @@ struct RenderBwdParams {
     uint32_t *live_valid;  // 1 when this composite marked the live flags, 0 when it did not (read by preprocess_bwd)
     uint4 *stamps;  // diagnostics (set by launch), or null
     int strip_exact;  // as RenderFwdParams::strip_exact (set by launch)
+    int definite_fast;  // as RenderFwdParams::definite_fast (set by launch)
     uint64_t num_rendered = 0;  // instances (the launch's walk-variant choice)
     // segmented walk (small images): the forward's checkpoints, or null for one wave (or workgroup) per tile
     const float *ckpt = nullptr, *ctot = nullptr;
