@@ -176,6 +176,8 @@ EXPORTED_SYMBOLS = (
     "gsr_bilagrid_workspace_bytes", "gsr_bilagrid_slice_forward", "gsr_bilagrid_slice_backward",
     "gsr_bilagrid_tv_num_partials", "gsr_bilagrid_tv_forward", "gsr_bilagrid_tv_backward",
     "gsr_mipfilter_rate", "gsr_activations_filter3d_forward", "gsr_activations_filter3d_backward",
+    "gsr_geomfeat_forward", "gsr_geomfeat_backward", "gsr_normal_consistency_forward", "gsr_depth_to_normal",
+    "gsr_normal_consistency_backward",
 )
 
 _lib = None
@@ -272,6 +274,16 @@ def load(path: str | None = None):
         lib.gsr_activations_filter3d_forward.restype = ctypes.c_int
         lib.gsr_activations_filter3d_backward.argtypes = [ctypes.c_int64] + [_fp] * 10 + [ctypes.c_void_p]
         lib.gsr_activations_filter3d_backward.restype = ctypes.c_int
+    if hasattr(lib, "gsr_geomfeat_forward"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
+        image = [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float]  # H, W, tanfovx, tanfovy
+        lib.gsr_geomfeat_forward.argtypes = [ctypes.c_int64] + [_fp] * 5 + [ctypes.c_void_p]
+        lib.gsr_geomfeat_backward.argtypes = [ctypes.c_int64] + [_fp] * 7 + [ctypes.c_void_p]
+        lib.gsr_normal_consistency_forward.argtypes = image + [_fp] * 5 + [ctypes.c_void_p]
+        lib.gsr_depth_to_normal.argtypes = image + [_fp] * 3 + [ctypes.c_void_p]
+        lib.gsr_normal_consistency_backward.argtypes = image + [_fp] * 7 + [ctypes.c_void_p]
+        for fn in (lib.gsr_geomfeat_forward, lib.gsr_geomfeat_backward, lib.gsr_normal_consistency_forward,
+                   lib.gsr_depth_to_normal, lib.gsr_normal_consistency_backward):
+            fn.restype = ctypes.c_int
     lib.gsr_mark_visible.argtypes = [ctypes.c_int, _fp, _fp, _fp, _fp, ctypes.c_void_p]
     lib.gsr_mark_visible.restype = ctypes.c_int
     lib.gsr_sh_backward_views.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp,

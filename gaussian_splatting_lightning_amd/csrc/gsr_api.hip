@@ -2185,6 +2185,103 @@ int gsr_activations_filter3d_backward(int64_t N, const float *scaling, const flo
     return GSR_OK;
 }
 
+// ---- normal consistency (gsr_normals.hip) ----
+static const char *geomfeat_error(int64_t P, const void *const *ptrs, int n, const void *const *quads, int nq) {
+    if (P < 0 || P > 0x7fffffffLL * 256) return "geomfeat: bad P";
+    for (int i = 0; i < n; i++)
+        if (!ptrs[i]) return "geomfeat: null array";
+    for (int i = 0; i < nq; i++)
+        if (!aligned16(quads[i])) return "geomfeat: the (P,4) arrays must be 16-B aligned";
+    return nullptr;
+}
+
+int gsr_geomfeat_forward(int64_t P, const float *means3D, const float *scales, const float *rotations,
+                         const float *viewmatrix, float *out, void *stream_ptr) {
+    const void *ptrs[] = {means3D, scales, rotations, viewmatrix, out}, *quads[] = {rotations, out};
+    if (const char *e = geomfeat_error(P, ptrs, 5, quads, 2)) return fail(GSR_ERR_ARG, e);
+    if (P == 0) return GSR_OK;
+    GeomfeatArgs A{};
+    A.P = P;
+    A.means3D = means3D; A.scales = scales; A.rotations = rotations; A.viewmatrix = viewmatrix;
+    A.out = out;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_geomfeat_forward((hipStream_t)stream_ptr, A);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_geomfeat_backward(int64_t P, const float *means3D, const float *scales, const float *rotations,
+                          const float *viewmatrix, const float *dL_dout, float *dL_dmeans3D, float *dL_drotations,
+                          void *stream_ptr) {
+    const void *ptrs[] = {means3D, scales, rotations, viewmatrix, dL_dout, dL_dmeans3D, dL_drotations};
+    const void *quads[] = {rotations, dL_dout, dL_drotations};
+    if (const char *e = geomfeat_error(P, ptrs, 7, quads, 3)) return fail(GSR_ERR_ARG, e);
+    if (P == 0) return GSR_OK;
+    GeomfeatArgs A{};
+    A.P = P;
+    A.means3D = means3D; A.scales = scales; A.rotations = rotations; A.viewmatrix = viewmatrix;
+    A.dL_dout = dL_dout; A.dL_dmeans3D = dL_dmeans3D; A.dL_drotations = dL_drotations;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_geomfeat_backward((hipStream_t)stream_ptr, A);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+static const char *normal_shape_error(int H, int W, float tanfovx, float tanfovy) {
+    if (H <= 0 || W <= 0) return "normal consistency: H and W must be positive";
+    if ((int64_t)H * W > 0x7fffffffLL || (H + 3) / 4 > 65535) return "normal consistency: image too large";
+    if (!std::isfinite(tanfovx) || !std::isfinite(tanfovy) || !(tanfovx > 0.f) || !(tanfovy > 0.f))
+        return "normal consistency: tanfovx and tanfovy must be finite and positive";
+    return nullptr;
+}
+
+static NormalArgs normal_args(int H, int W, float tanfovx, float tanfovy) {
+    NormalArgs A{};
+    A.H = H; A.W = W;
+    A.ifx = (float)(2.0 * (double)tanfovx / W);
+    A.ify = (float)(2.0 * (double)tanfovy / H);
+    A.cx = (float)(0.5 - 0.5 * W);
+    A.cy = (float)(0.5 - 0.5 * H);
+    return A;
+}
+
+int gsr_normal_consistency_forward(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A,
+                                   const float *N, float *E, float *n_d, void *stream_ptr) {
+    if (const char *e = normal_shape_error(H, W, tanfovx, tanfovy)) return fail(GSR_ERR_ARG, e);
+    if (!D || !A || !N || !E) return fail(GSR_ERR_ARG, "normal consistency: null array");
+    NormalArgs a = normal_args(H, W, tanfovx, tanfovy);
+    a.D = D; a.A = A; a.N = N; a.E = E; a.n_d = n_d;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_normal_consistency_forward((hipStream_t)stream_ptr, a);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_depth_to_normal(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A, float *n_d,
+                        void *stream_ptr) {
+    if (const char *e = normal_shape_error(H, W, tanfovx, tanfovy)) return fail(GSR_ERR_ARG, e);
+    if (!D || !A || !n_d) return fail(GSR_ERR_ARG, "normal consistency: null array");
+    NormalArgs a = normal_args(H, W, tanfovx, tanfovy);
+    a.D = D; a.A = A; a.n_d = n_d;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_normal_consistency_forward((hipStream_t)stream_ptr, a);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_normal_consistency_backward(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A,
+                                    const float *N, const float *dE, float *dD, float *dA, float *dN,
+                                    void *stream_ptr) {
+    if (const char *e = normal_shape_error(H, W, tanfovx, tanfovy)) return fail(GSR_ERR_ARG, e);
+    if (!D || !A || !N || !dE || !dD || !dA || !dN) return fail(GSR_ERR_ARG, "normal consistency: null array");
+    NormalArgs a = normal_args(H, W, tanfovx, tanfovy);
+    a.D = D; a.A = A; a.N = N; a.dE = dE; a.dD = dD; a.dA = dA; a.dN = dN;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_normal_consistency_backward((hipStream_t)stream_ptr, a);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
 int gsr_mark_visible(int P, const float *means3D, const float *viewmatrix, const float *projmatrix, uint8_t *present,
                      void *stream_ptr) {
     (void)projmatrix;

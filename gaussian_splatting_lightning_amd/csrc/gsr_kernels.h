@@ -617,4 +617,28 @@ struct Filter3DArgs {
 void launch_activations_filter3d_forward(hipStream_t s, const Filter3DArgs &A);
 void launch_activations_filter3d_backward(hipStream_t s, const Filter3DArgs &A);
 
+// ---- normal consistency: geometry features, depth normals and the loss map (gsr_normals.hip) ----
+struct GeomfeatArgs {
+    int64_t P;
+    const float *means3D, *scales, *rotations;  // (P,3) (P,3) activated, (P,4) (w,x,y,z) unnormalised
+    const float *viewmatrix;                    // (4,4) row vectors, on the device
+    float *out;                                 // forward: (P,4) = (n_v, z)
+    const float *dL_dout;                       // backward: (P,4)
+    float *dL_dmeans3D, *dL_drotations;         // backward: (P,3) (P,4)
+};
+void launch_geomfeat_forward(hipStream_t s, const GeomfeatArgs &A);
+void launch_geomfeat_backward(hipStream_t s, const GeomfeatArgs &A);
+
+struct NormalArgs {
+    int H, W;
+    float ifx, ify;           // 2 tanfovx / W, 2 tanfovy / H
+    float cx, cy;             // 0.5 - W/2, 0.5 - H/2: the ray of pixel (x, y) is ((x + cx) ifx, (y + cy) ify, 1)
+    const float *D, *A, *N;   // (1,H,W) (1,H,W) (3,H,W)
+    float *E, *n_d;           // forward: (1,H,W), (3,H,W); either may be null
+    const float *dE;          // backward: (1,H,W)
+    float *dD, *dA, *dN;      // backward: (1,H,W) (1,H,W) (3,H,W)
+};
+void launch_normal_consistency_forward(hipStream_t s, const NormalArgs &A);
+void launch_normal_consistency_backward(hipStream_t s, const NormalArgs &A);
+
 }  // namespace gsr

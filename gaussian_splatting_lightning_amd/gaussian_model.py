@@ -18,6 +18,7 @@ working: `_xyz`, `_features_dc`, `_features_rest`, `_opacity`, `_scaling`, `_rot
 * `compute_3d_filter(cameras)`, `get_activated(filter_3d=True)`, `get_scaling_with_3D_filter`,
   `get_opacity_with_3D_filter`, `save_ply(with_filter=True)`, `save_fused_ply` -- mipfilter.py: Mip-Splatting's 3D
   smoothing filter as the `filter_3D` buffer and one fused launch for the filtered activations;
+* `get_geometry_features(settings)` -- normals.py: the (N,4) normal-and-depth block of the normal-consistency loss;
 * `reset_opacity`, `reset_max_radii2D`, `reset_xyz_gradient`, `step_sh_degree`, `ready_for_*`.
 
 `spatial_scale` is passed directly (the reference derives it from COLMAP cameras with pycolmap,
@@ -32,6 +33,7 @@ from torch import nn
 
 from . import densify as _densify
 from . import mipfilter as _mip
+from . import normals as _normals
 from . import ply as _ply
 from .activations import GaussianActivations
 from .knn import dist_cuda2
@@ -169,6 +171,13 @@ class GaussianModel(nn.Module):
             f = self._filter()
             return FilteredGaussianActivations.apply(self._scaling, self._opacity, self._rotation, f)
         return GaussianActivations.apply(self._scaling, self._opacity, self._rotation)
+
+    def get_geometry_features(self, settings, filter_3d: bool = False) -> torch.Tensor:
+        """(N,4) = (view-space normal facing the camera, view depth) per Gaussian, the block to render with `features=`
+        for the normal-consistency loss (normals.geometry_features; `settings` a GaussianRasterizationSettings or a
+        (4,4) viewmatrix).  One launch after the activations', one more each in the backward."""
+        scales, _, rotations = self.get_activated(filter_3d=filter_3d)
+        return _normals.geometry_features(self._xyz, scales, rotations, settings)
 
     def get_scaling_with_3D_filter(self) -> torch.Tensor:
         return self.get_activated(filter_3d=True)[0]

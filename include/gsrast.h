@@ -590,6 +590,45 @@ int gsr_activations_filter3d_backward(int64_t N, const float *scaling, const flo
                                       const float *dL_drotations, float *dL_dscaling, float *dL_dopacity,
                                       float *dL_drotation, void *stream);
 
+/* Normal consistency (2DGS, Huang et al., SIGGRAPH 2024): the normals rendered from the Gaussians against the normals
+ * of the rendered depth surface.  Only functions are added: GSR_ABI_VERSION and every struct stay as they are.  All five
+ * return GSR_ERR_ARG before any device work on a NULL required pointer, a negative P, H <= 0 or W <= 0, H * W above
+ * 2^31 - 1, or a tanfov that is not finite and positive.  Conventions are the rasterizer's: row vectors (p_view =
+ * [p, 1] viewmatrix), quaternions (w,x,y,z), pixel (x, y) looks along r(x, y) = ((x + 0.5 - W/2) / fx,
+ * (y + 0.5 - H/2) / fy, 1) with fx = W / (2 tanfovx), fy = H / (2 tanfovy) (a centred principal point).
+ *
+ * gsr_geomfeat_forward: out (P,4), the feature block to render with gsr_features_ext.  Per Gaussian i, k = the index of
+ *   the smallest of scales[i] (activated; the first on a tie), n_w = column k of R(q / max(|q|, 1e-12)) with R as the
+ *   covariance is built from rotations[i], n_v = n_w viewmatrix[:3,:3], z = p_view.z, n_v negated where
+ *   n_v . p_view[:3] > 0 (it faces the camera): out[i] = (n_v, z).  means3D, scales (P,3); rotations, out (P,4), 16-B
+ *   aligned; viewmatrix (4,4) on the device.  One launch, no atomics; nothing is launched (GSR_OK) at P == 0.
+ * gsr_geomfeat_backward: dL_dmeans3D (P,3) (through z only) and dL_drotations (P,4) (through n_v and the
+ *   normalisation) from dL_dout (P,4) and the forward's inputs; k and the flip are recomputed (piecewise constant, so
+ *   scales take no gradient, and neither does viewmatrix here).  Both outputs are written whole.
+ *
+ * gsr_normal_consistency_forward: D (1,H,W) the rendered sum of w z (feature channel 3), A (1,H,W) the rendered alpha,
+ *   N (3,H,W) the rendered normals (feature channels 0-2, not normalised).  d = D / A where A > 0, else 0;
+ *   Pt(x, y) = d r(x, y);  c = (Pt(x, y+1) - Pt(x, y-1)) x (Pt(x+1, y) - Pt(x-1, y));  n_d = c / |c|, and 0 where
+ *   |c| = 0 and on the one-pixel border (2DGS's depth_to_normal: a fronto-parallel surface has n_d = (0, 0, -1));
+ *   E = 1 - A (N . n_d), exactly 1 where n_d = 0.  E (1,H,W) is written whole, and n_d (3,H,W) too unless it is NULL.
+ * gsr_depth_to_normal: n_d alone, the same bits.
+ * gsr_normal_consistency_backward: dD, dA (1,H,W) and dN (3,H,W) from dE (1,H,W) with the factor A of E held constant
+ *   (2DGS detaches it): dN = -dE A n_d, and D and A take their gradient through d only; where |c| = 0 the normal's
+ *   gradient is zero.  A gather: every pixel sums, in a fixed order, what it contributes to the normals of its four
+ *   neighbours, whose cross products are recomputed from D and A; nothing is saved by the forward.  No atomics, every
+ *   output element is written exactly once (zeros included), two calls give the same bits. */
+int gsr_geomfeat_forward(int64_t P, const float *means3D, const float *scales, const float *rotations,
+                         const float *viewmatrix, float *out, void *stream);
+int gsr_geomfeat_backward(int64_t P, const float *means3D, const float *scales, const float *rotations,
+                          const float *viewmatrix, const float *dL_dout, float *dL_dmeans3D, float *dL_drotations,
+                          void *stream);
+int gsr_normal_consistency_forward(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A,
+                                   const float *N, float *E, float *n_d, void *stream);
+int gsr_depth_to_normal(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A, float *n_d,
+                        void *stream);
+int gsr_normal_consistency_backward(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A,
+                                    const float *N, const float *dE, float *dD, float *dA, float *dN, void *stream);
+
 /* PLY vertex records <-> parameter fields (the 3DGS checkpoint of gaussian_model.py:112-171 and
  * third_party/.../gaussian_model.py:239-314).  `records` are n fixed-size records of record_bytes each, on the
  * device; `columns` (host array, destination order: field after field, column after column) give each
