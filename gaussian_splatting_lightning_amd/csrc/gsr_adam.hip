@@ -129,7 +129,11 @@ __global__ __launch_bounds__(256) void activations_forward_kernel(ActivationArgs
     if (i >= A.N) return;
 #pragma unroll
     for (int k = 0; k < 3; k++) A.scales[3 * i + k] = expf(A.scaling[3 * i + k]);
-    A.opacities[i] = 1.0f / (1.0f + expf(-A.opacity[i]));
+    // 1 / (1 + e^-x).  Below x = -88.7 e^-x overflows and the quotient would flush the (subnormal) sigmoid to 0;
+    // there 1 + e^x rounds to 1 and the value is e^x.  Every other input keeps the plain form's bits.  Deliberately
+    // not torch.sigmoid there, which returns that 0: the two differ by less than 1e-38.
+    const float x = A.opacity[i], ex = expf(-x);
+    A.opacities[i] = ex > 3.402823466e+38f ? expf(x) : 1.0f / (1.0f + ex);
     const float4 q = *reinterpret_cast<const float4 *>(A.rotation + 4 * i);
     const float n = fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), NORMALIZE_EPS);
     *reinterpret_cast<float4 *>(A.rotations + 4 * i) = make_float4(q.x / n, q.y / n, q.z / n, q.w / n);

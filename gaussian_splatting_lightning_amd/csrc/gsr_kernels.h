@@ -402,12 +402,15 @@ void launch_sh_backward_views(hipStream_t s, int P, int D, int M, int V, int chu
 // Adam so the two give the same bits: the contractions are explicit (the compiler's choice of FMA could differ between
 // the kernels otherwise):
 //     m = lerp(m, g, 1 - b1);  v = v b2 + (1 - b2) g^2;  p -= step_size * m / (sqrt(v) / sqrt(bc2) + eps)
+// Bitwise torch.optim.Adam's step on this device (tests/test_adam.py): mul_(beta2) is a kernel of its own, so v b2
+// is rounded before addcmul_ contracts value * (g g) + v; sqrtf is the correctly rounded root (__fsqrt_rn is the
+// hardware's approximate one here).
 __device__ __forceinline__ void adam_update(float &p, float g, float &m, float &v, float b1c, float b2, float b2c,
                                             float step_size, float bc2_sqrt, float eps) {
 #pragma clang fp contract(off)
     m = __fmaf_rn(b1c, __fsub_rn(g, m), m);                // exp_avg.lerp_(grad, 1 - beta1)
-    v = __fmaf_rn(v, b2, __fmul_rn(b2c, __fmul_rn(g, g)));  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), bc2_sqrt), eps);
+    v = __fmaf_rn(b2c, __fmul_rn(g, g), __fmul_rn(v, b2));  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    const float denom = __fadd_rn(__fdiv_rn(sqrtf(v), bc2_sqrt), eps);
     p = __fmaf_rn(-step_size, __fdiv_rn(m, denom), p);     // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
