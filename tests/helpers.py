@@ -63,8 +63,11 @@ def settings_for(inp: dict, device, antialiasing=False, debug=False):
 
 
 def run_hip(inp: dict, device, dL_dcolor=None, dL_dinvdepth=None, colors_precomp=None, cov3D_precomp=None,
-            antialiasing=False, debug=False):
-    """HIP forward (+ backward when dL_dcolor is given) through forward_raw/backward_raw."""
+            antialiasing=False, debug=False, flip_mask=None):
+    """HIP forward (+ backward when dL_dcolor is given) through forward_raw/backward_raw.  With `flip_mask` (H, W bool:
+    the oracle's threshold-flip candidate pixels, known before this run) that has a pixel set, a second backward on
+    the same forward state, under whatever knobs the caller holds, with the upstream gradients zeroed on those pixels:
+    out["grads_masked"] (tests/test_gpu_parity.py compare_backward's masked leg)."""
     from gaussian_splatting_lightning_amd.rasterizer import backward_raw, forward_raw
     t = lambda a: None if a is None else torch.as_tensor(np.asarray(a, np.float32), device=device)  # noqa: E731
     rs = settings_for(inp, device, antialiasing=antialiasing, debug=debug)
@@ -78,6 +81,10 @@ def run_hip(inp: dict, device, dL_dcolor=None, dL_dinvdepth=None, colors_precomp
     if dL_dcolor is not None:
         g = backward_raw(st, rs, t(dL_dcolor), t(dL_dinvdepth))
         out["grads"] = {k: (v.cpu().numpy() if v is not None else None) for k, v in g.items()}
+        if flip_mask is not None and np.any(flip_mask):
+            keep = t(~np.asarray(flip_mask, bool))
+            g = backward_raw(st, rs, t(dL_dcolor) * keep, None if dL_dinvdepth is None else t(dL_dinvdepth) * keep)
+            out["grads_masked"] = {k: (v.cpu().numpy() if v is not None else None) for k, v in g.items()}
     torch.cuda.synchronize()
     return out
 

@@ -8,7 +8,10 @@ composed from it by linearity.  With upstream gradients (g, di, a) of (colour, i
 so the truth is the oracle's run A (background 0, SH colours, backward(g, di)) plus its run B (colours 0, background 1,
 so colour channel 0 IS T_final; backward((tau, 0, 0))); dL/dshs is run A alone.  The composition's own error is
 measured from the oracle alone on the vector background without alpha, where the oracle has a direct answer, recorded,
-and added to the clean bar; no bar is fitted to HIP output.  Achieved figures: profiles/parity_alpha.json.
+and added to the clean bar; no bar is fitted to HIP output.  Achieved figures: profiles/parity_alpha.json.  As in
+tests/test_gpu_parity.py compare_backward, a second backward on the same forward with all three upstream gradients
+zeroed on the oracle's flip candidates is held to that clean bar over ALL Gaussians, against truth - g_flip (the
+composition is linear in (g, di, a)); figures in profiles/parity_masked.json.
 
 Selections: those of tests/test_edge_parity.py plus the union walk and 32-instance segments.  The union walk is a form
 of the whole-tile kernel, so its selection is the whole-tile one with bwd_union=1 (at this image size bwd_union alone
@@ -23,8 +26,8 @@ import torch
 from tests import parity
 from tests.helpers import hip_state_arrays, rel_l2, run_hip, run_oracle, scene_inputs, settings_for, upstream
 from tests.test_edge_parity import SELECTIONS as EDGE_SELECTIONS
-from tests.test_gpu_parity import (COLOR_TOL, FLIP_MARGIN, FLIP_PROPAGATION, FLIP_TOL, GRAD_CLEAN_TOL, GRADS, _case,
-                                   compare_forward)
+from tests.test_gpu_parity import (COLOR_TOL, FLIP_MARGIN, FLIP_PIXEL_CAP, FLIP_PROPAGATION, FLIP_TOL, GRAD_CLEAN_TOL,
+                                   GRADS, _case, compare_forward)
 
 pytestmark = pytest.mark.gpu
 
@@ -84,7 +87,8 @@ def _residual():
 
 @functools.lru_cache(maxsize=None)
 def _case_inputs(case):
-    """(g, di, a, background) of one case and its composed truth, with the flip candidates' share g_flip."""
+    """(g, di, a, background) of one case and its composed truth, with the flip candidates' share g_flip and their
+    mask."""
     inp, dc, di, da, image = _base()
     g, d = (None, None) if case == "alpha_only" else (dc, di)
     bg = image if case == "alpha_bg_image" else np.asarray(BG, f32)
@@ -96,7 +100,7 @@ def _case_inputs(case):
     flip = (_oracle()[0][3].threshold_margin() < FLIP_MARGIN).astype(f32)
     truth = _compose(g, d, tau)
     g_flip = _compose(None if g is None else g * flip[None], None if d is None else d * flip[None], tau * flip)
-    return g, d, da, bg, truth, g_flip
+    return g, d, da, bg, truth, g_flip, flip.astype(bool)
 
 
 def _t(a, dev):
@@ -206,25 +210,39 @@ def test_gradients_vs_composed_oracle(gpu_device, case, selection):
     from gaussian_splatting_lightning_amd import _native
     from gaussian_splatting_lightning_amd.rasterizer import backward_raw
     inp = _base()[0]
-    g, d, da, bg, truth, g_flip = _case_inputs(case)
+    g, d, da, bg, truth, g_flip, flip = _case_inputs(case)
     residual = _residual()
     with _native.tuned(**SELECTIONS[selection]):
         # the flip census of this selection's own forward (compare_forward: integer state, colour, touched Gaussians)
         run = compare_forward(inp, run_hip(inp, gpu_device), _oracle()[0])
         rs, (_, _, _, _, st) = _forward(inp, gpu_device, bg=bg)
         got = _np(backward_raw(st, rs, _t(g, gpu_device), _t(d, gpu_device), grad_out_alpha=_t(da, gpu_device)))
+        got_m = None
+        if flip.any():  # the masked leg (compare_backward): every upstream gradient zeroed on the flip candidates
+            keep = (~flip).astype(f32)[None]
+            got_m = _np(backward_raw(st, rs, _t(None if g is None else g * keep, gpu_device),
+                                     _t(None if d is None else d * keep, gpu_device),
+                                     grad_out_alpha=_t(da * keep, gpu_device)))
     clean = ~run.flip_touched
-    rec = {"touched_gaussians": int(run.flip_touched.sum()), "flip_pixels": int(run.flip_mask.sum())}
+    rec = {"touched_gaussians": int(run.flip_touched.sum()), "flip_pixels": int(run.flip_mask.sum()),
+           "flip_pixel_share": float(flip.mean())}
     for k in GRADS:
         want = truth[k].reshape(got[k].shape)
         norm = float(np.linalg.norm(want))
         rec[k] = dict(rel_l2=rel_l2(got[k], want), rel_l2_clean=rel_l2(got[k][clean], want[clean]),
                       bar=GRAD_CLEAN_TOL + FLIP_PROPAGATION * float(np.linalg.norm(g_flip[k])) / max(norm, 1e-30),
                       bar_clean=GRAD_CLEAN_TOL + residual[k])
+        if got_m is not None:  # the composed truth is linear in (g, d, da): masked truth = truth - g_flip
+            want_m = (truth[k] - g_flip[k]).reshape(got[k].shape)
+            rec[k].update(rel_l2_masked=rel_l2(got_m[k], want_m),
+                          rel_l2_masked_touched=rel_l2(got_m[k][~clean], want_m[~clean]))
     parity.record(_case(), "backward", rec)
+    assert rec["flip_pixel_share"] <= FLIP_PIXEL_CAP, rec
     for k in GRADS:
         assert rec[k]["rel_l2_clean"] <= rec[k]["bar_clean"], (k, rec[k])
         assert rec[k]["rel_l2"] <= rec[k]["bar"], (k, rec[k])
+        if got_m is not None:  # all Gaussians, the touched ones included, at the clean bar
+            assert rec[k]["rel_l2_masked"] <= rec[k]["bar_clean"], (k, rec[k])
 
 
 def test_background_image(gpu_device):

@@ -3,7 +3,8 @@
 and non-unit quaternions, opacities at 0, 1/255 and 1, tile rectangles clamped to the whole grid).
 
   * HIP against the oracle on every case, through tests/test_gpu_parity.py's compare_forward / compare_backward
-    unchanged (bit-exact integer state and render records, COLOR_TOL, GRAD_CLEAN_TOL, the derived all-Gaussian bar),
+    unchanged (bit-exact integer state and render records, COLOR_TOL, GRAD_CLEAN_TOL, the derived all-Gaussian bar,
+    and GRAD_CLEAN_TOL over all Gaussians with the flip candidates' upstream gradients masked where a case has any),
     under four selections so that every composite kernel sees the edges: the default (segmented walk at these image
     sizes), the threshold guard, the whole-tile walk and the part-wave walk;
   * HIP against the reference's fixture tests/golden/edges.npz with the reference bars of the CPU leg
@@ -21,7 +22,7 @@ from tests import edge_cases as E
 from tests import parity
 from tests.helpers import hip_state_arrays, rel_l2, run_hip, run_oracle
 from tests.test_edge_cases import floor_equivalence
-from tests.test_gpu_parity import GRADS, _case, compare_backward, compare_forward
+from tests.test_gpu_parity import GRADS, _case, compare_backward, compare_forward, flip_candidates
 
 pytestmark = pytest.mark.gpu
 
@@ -44,7 +45,8 @@ def test_edge_case_vs_oracle(gpu_device, name, selection):
     from gaussian_splatting_lightning_amd import _native
     inp, dc, di, oracle_out = _scene(name)
     with _native.tuned(**SELECTIONS[selection]):
-        hip = run_hip(inp, gpu_device, dc, di, antialiasing=E.antialiased(name))
+        hip = run_hip(inp, gpu_device, dc, di, antialiasing=E.antialiased(name),
+                      flip_mask=flip_candidates(oracle_out[3]))  # the masked backward under this selection too
     run = compare_forward(inp, hip, oracle_out)
     g = compare_backward(hip, run, dc, di)
     if selection == "guard":
