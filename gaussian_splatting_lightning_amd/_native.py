@@ -90,6 +90,16 @@ class DistortionExt(ctypes.Structure):  # include/gsrast.h gsr_distortion_ext (v
 
 
 DISTORTION_MAPS = {"z": 0, "ndc": 1}  # include/gsrast.h GSR_DISTORTION_Z, GSR_DISTORTION_NDC
+
+
+class MedianExt(ctypes.Structure):  # include/gsrast.h gsr_median_ext (versioned by struct_size)
+    _fields_ = [("struct_size", ctypes.c_size_t), ("out_median_depth", _fp), ("out_median_index", _fp),
+                ("median_pos", _fp), ("dL_dmedian_depth", _fp)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=ctypes.sizeof(MedianExt), **fields)
+
+
 GSR_BUF_CONTRIB_SCRATCH = 6
 
 
@@ -178,6 +188,8 @@ EXPORTED_SYMBOLS = (
     "gsr_mipfilter_rate", "gsr_activations_filter3d_forward", "gsr_activations_filter3d_backward",
     "gsr_geomfeat_forward", "gsr_geomfeat_backward", "gsr_normal_consistency_forward", "gsr_depth_to_normal",
     "gsr_normal_consistency_backward",
+    "gsr_forward_median", "gsr_backward_median", "gsr_normal_consistency_forward_surface",
+    "gsr_depth_to_normal_surface", "gsr_normal_consistency_backward_surface",
 )
 
 _lib = None
@@ -233,6 +245,26 @@ def load(path: str | None = None):
                                                 ctypes.POINTER(DistortionExt), ALLOC_FN, ctypes.c_void_p,
                                                 ctypes.c_void_p]
         lib.gsr_backward_distortion.restype = ctypes.c_int
+    if hasattr(lib, "gsr_forward_median"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
+        lib.gsr_forward_median.argtypes = [ctypes.POINTER(ForwardArgs), ctypes.POINTER(CompositeExt),
+                                           ctypes.POINTER(FeaturesExt), ctypes.POINTER(DistortionExt),
+                                           ctypes.POINTER(MedianExt), ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.POINTER(ctypes.c_int64)]
+        lib.gsr_forward_median.restype = ctypes.c_int
+        lib.gsr_backward_median.argtypes = [ctypes.POINTER(BackwardArgs), ctypes.POINTER(CompositeExt),
+                                            ctypes.POINTER(AbsgradExt), ctypes.POINTER(FeaturesExt),
+                                            ctypes.POINTER(DistortionExt), ctypes.POINTER(MedianExt), ALLOC_FN,
+                                            ctypes.c_void_p, ctypes.c_void_p]
+        lib.gsr_backward_median.restype = ctypes.c_int
+        image = [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float]  # H, W, tanfovx, tanfovy
+        lib.gsr_normal_consistency_forward_surface.argtypes = image + [_fp] * 4 + [ctypes.c_float, _fp, _fp,
+                                                                                   ctypes.c_void_p]
+        lib.gsr_depth_to_normal_surface.argtypes = image + [_fp] * 3 + [ctypes.c_float, _fp, ctypes.c_void_p]
+        lib.gsr_normal_consistency_backward_surface.argtypes = image + [_fp] * 4 + [ctypes.c_float] + [_fp] * 5 + [
+            ctypes.c_void_p]
+        for fn in (lib.gsr_normal_consistency_forward_surface, lib.gsr_depth_to_normal_surface,
+                   lib.gsr_normal_consistency_backward_surface):
+            fn.restype = ctypes.c_int
     if hasattr(lib, "gsr_contributions"):  # absent from earlier builds loaded for A/Bs through GSR_LIB
         lib.gsr_contributions.argtypes = [ctypes.POINTER(ContribArgs), ALLOC_FN, ctypes.c_void_p, ctypes.c_void_p]
         lib.gsr_contributions.restype = ctypes.c_int
@@ -389,13 +421,16 @@ def _ref(struct):
     return None if struct is None else ctypes.byref(struct)
 
 
-def call_forward(lib, args, ext, feat, cb, stream, num_rendered, dist=None) -> int:
+def call_forward(lib, args, ext, feat, cb, stream, num_rendered, dist=None, median=None) -> int:
     """The forward through the narrowest entry point whose extra arguments are all given: gsr_forward, gsr_forward_ext
-    (ext: CompositeExt), gsr_forward_features (feat: FeaturesExt, ext given or None) or gsr_forward_distortion (dist:
-    DistortionExt, ext and feat given or None).  Which one is behaviour: at
+    (ext: CompositeExt), gsr_forward_features (feat: FeaturesExt, ext given or None), gsr_forward_distortion (dist:
+    DistortionExt, ext and feat given or None) or gsr_forward_median (median: MedianExt, the others given or None).
+    Which one is behaviour: at
     P == 0 the plain call returns zeros where the ext call returns the background.  The entry point is looked up on
     `lib` here, at call time, so a patched attribute is what runs."""
     a, n = ctypes.byref(args), ctypes.byref(num_rendered)
+    if median is not None:
+        return lib.gsr_forward_median(a, _ref(ext), _ref(feat), _ref(dist), ctypes.byref(median), cb, None, stream, n)
     if dist is not None:
         return lib.gsr_forward_distortion(a, _ref(ext), _ref(feat), ctypes.byref(dist), cb, None, stream, n)
     if feat is not None:
@@ -405,11 +440,14 @@ def call_forward(lib, args, ext, feat, cb, stream, num_rendered, dist=None) -> i
     return lib.gsr_forward(a, cb, None, stream, n)
 
 
-def call_backward(lib, args, ext, absgrad, feat, cb, stream, dist=None) -> int:
+def call_backward(lib, args, ext, absgrad, feat, cb, stream, dist=None, median=None) -> int:
     """The backward likewise: gsr_backward, gsr_backward_ext (ext), gsr_backward_abs (absgrad: AbsgradExt, ext given or
-    None), gsr_backward_features (feat: FeaturesExt, ext and absgrad given or None) or gsr_backward_distortion (dist:
-    DistortionExt, the others given or None)."""
+    None), gsr_backward_features (feat: FeaturesExt, ext and absgrad given or None), gsr_backward_distortion (dist:
+    DistortionExt, the others given or None) or gsr_backward_median (median: MedianExt, the others given or None)."""
     a = ctypes.byref(args)
+    if median is not None:
+        return lib.gsr_backward_median(a, _ref(ext), _ref(absgrad), _ref(feat), _ref(dist), ctypes.byref(median), cb,
+                                       None, stream)
     if dist is not None:
         return lib.gsr_backward_distortion(a, _ref(ext), _ref(absgrad), _ref(feat), ctypes.byref(dist), cb, None,
                                            stream)

@@ -103,6 +103,8 @@ enum Stage {
     ST_BACKGROUND_GRAD,
     ST_DIST_FWD,
     ST_DIST_BWD,
+    ST_MEDIAN_FWD,
+    ST_MEDIAN_BWD,
     ST_FEAT_FWD,
     ST_FEAT_BWD,
     ST_FEAT_GATHER,
@@ -115,6 +117,7 @@ const char *kStageNames[ST_COUNT] = {"preprocess", "depth_sort", "instance_scan"
                                      "render_bwd", "big_reduce", "preprocess_bwd", "sh_views",
                                      "bucket_count", "bucket_scatter", "seg_sort", "adam_sh_views",
                                      "background_grad", "distortion_fwd", "distortion_bwd",
+                                     "median_fwd", "median_bwd",
                                      "feat_fwd", "feat_bwd", "feat_gather",
                                      "contrib_walk", "contrib_gather"};
 
@@ -494,6 +497,27 @@ int read_distortion_ext(const gsr_distortion_ext *x, DistortionExt &d) {
         return fail(GSR_ERR_ARG, "gsr_distortion_ext: total_weight and total_moment are required");
     return GSR_OK;
 }
+// gsr_median_ext as the library reads it
+struct MedianExt {
+    bool given = false;
+    float *out_depth = nullptr;
+    int32_t *out_index = nullptr, *pos = nullptr;
+    const float *dL_dmedian = nullptr;
+};
+// the checks both directions share: the struct's size and the position plane
+int read_median_ext(const gsr_median_ext *x, MedianExt &m) {
+    if (!x) return GSR_OK;
+    const VersionedIn<gsr_median_ext> in(x);
+    if (!in.covers(&gsr_median_ext::out_median_depth))
+        return fail(GSR_ERR_ARG, "gsr_median_ext: struct_size ends before the first pointer field");
+    m.given = true;
+    m.out_depth = in.get(&gsr_median_ext::out_median_depth);
+    m.out_index = in.get(&gsr_median_ext::out_median_index);
+    m.pos = in.get(&gsr_median_ext::median_pos);
+    m.dL_dmedian = in.get(&gsr_median_ext::dL_dmedian_depth);
+    if (!m.pos) return fail(GSR_ERR_ARG, "gsr_median_ext: median_pos is required");
+    return GSR_OK;
+}
 // far / (far - near) and far near / (far - near), formed in double and rounded once
 static float dist_k0(const DistortionExt &d) { return (float)((double)d.farp / ((double)d.farp - (double)d.nearp)); }
 static float dist_dscale(const DistortionExt &d) {
@@ -647,6 +671,7 @@ struct FwdCall : RasterState {
     CompositeExt e;
     FeaturesExt fx;
     DistortionExt dx;
+    MedianExt mx;
     int P;
     // the readback: this thread's pinned words and event, the sequence number awaited, and whether the preprocess
     // publishes into the words ("rb_spin") or a copy plus the event brings the counters
@@ -667,7 +692,7 @@ struct FwdCall : RasterState {
 
 // The side structs and every argument check, in the order callers see their errors
 static int fwd_check_args(FwdCall &c, const gsr_composite_ext *ext, const gsr_features_ext *feat,
-                          const gsr_distortion_ext *dist) {
+                          const gsr_distortion_ext *dist, const gsr_median_ext *median) {
     gsr_forward_args *a = c.a;
     int rc = read_composite_ext(ext, a->background, c.e);
     if (rc) return rc;
@@ -677,6 +702,10 @@ static int fwd_check_args(FwdCall &c, const gsr_composite_ext *ext, const gsr_fe
     rc = read_distortion_ext(dist, c.dx);
     if (rc) return rc;
     if (c.dx.given && !c.dx.out) return fail(GSR_ERR_ARG, "gsr_distortion_ext: out_distortion is required");
+    rc = read_median_ext(median, c.mx);
+    if (rc) return rc;
+    if (c.mx.given && (!c.mx.out_depth || !c.mx.out_index))
+        return fail(GSR_ERR_ARG, "gsr_median_ext: out_median_depth and out_median_index are required");
     rc = check_common(a->P, a->D, a->M, a->W, a->H, a->means3D, a->opacities, a->colors_precomp, a->shs,
                       a->scales, a->rotations, a->cov3D_precomp, a->viewmatrix, a->projmatrix, a->campos,
                       c.e.background_image ? c.e.background_image : a->background);
@@ -703,6 +732,11 @@ static int fwd_empty_scene(FwdCall &c) {
     if (c.fx.given) GSR_HIP(hipMemsetAsync(c.fx.out_features, 0, sizeof(float) * c.fx.C * HW, stream));
     if (c.dx.given)
         for (float *m : {c.dx.out, c.dx.tot_w, c.dx.tot_m}) GSR_HIP(hipMemsetAsync(m, 0, sizeof(float) * HW, stream));
+    if (c.mx.given) {  // no Gaussian reaches any pixel: depth 0, index and position -1
+        GSR_HIP(hipMemsetAsync(c.mx.out_depth, 0, sizeof(float) * HW, stream));
+        GSR_HIP(hipMemsetAsync(c.mx.out_index, 0xff, sizeof(int32_t) * HW, stream));
+        GSR_HIP(hipMemsetAsync(c.mx.pos, 0xff, sizeof(int32_t) * HW, stream));
+    }
     return GSR_OK;
 }
 
@@ -1050,6 +1084,17 @@ static int fwd_distortion(FwdCall &c) {
     return GSR_OK;
 }
 
+// The median depth, index and position planes, replayed likewise (tile_last = 0: 0, -1, -1)
+static int fwd_median(FwdCall &c) {
+    hipStream_t stream = c.stream;
+    MedianFwdParams mp;
+    mp.src = replay_src(c);
+    mp.depth_key = c.g.depth_key;
+    mp.out_depth = c.mx.out_depth; mp.out_index = c.mx.out_index; mp.out_pos = c.mx.pos;
+    GSR_STAGE(ST_MEDIAN_FWD, c.dbg, launch_median_fwd(stream, mp));
+    return GSR_OK;
+}
+
 int gsr_forward(gsr_forward_args *a, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr,
                 int64_t *num_rendered) {
     return gsr_forward_ext(a, nullptr, alloc, alloc_ctx, stream_ptr, num_rendered);
@@ -1068,11 +1113,17 @@ int gsr_forward_features(gsr_forward_args *a, const gsr_composite_ext *ext, cons
 int gsr_forward_distortion(gsr_forward_args *a, const gsr_composite_ext *ext, const gsr_features_ext *feat,
                            const gsr_distortion_ext *dist, gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr,
                            int64_t *num_rendered) {
+    return gsr_forward_median(a, ext, feat, dist, nullptr, alloc, alloc_ctx, stream_ptr, num_rendered);
+}
+
+int gsr_forward_median(gsr_forward_args *a, const gsr_composite_ext *ext, const gsr_features_ext *feat,
+                       const gsr_distortion_ext *dist, const gsr_median_ext *median, gsr_alloc_fn alloc,
+                       void *alloc_ctx, void *stream_ptr, int64_t *num_rendered) {
     if (!a || !alloc || !num_rendered) return fail(GSR_ERR_ARG, "null argument");
     FwdCall c{};
     c.a = a; c.alloc = alloc; c.alloc_ctx = alloc_ctx;
     c.stream = (hipStream_t)stream_ptr; c.dbg = a->debug != 0;
-    int rc = fwd_check_args(c, ext, feat, dist);
+    int rc = fwd_check_args(c, ext, feat, dist, median);
     if (rc) return rc;
     // Both live in this frame across every stage: the stream's device stays current until the call returns, and an
     // early return of any stage after the preprocess launch runs ~InflightReadback (a wait for the stream) before
@@ -1095,6 +1146,7 @@ int gsr_forward_distortion(gsr_forward_args *a, const gsr_composite_ext *ext, co
     if (!rc) rc = fwd_composite(c);
     if (!rc && c.fx.given) rc = fwd_features(c);
     if (!rc && c.dx.given) rc = fwd_distortion(c);
+    if (!rc && c.mx.given) rc = fwd_median(c);
     if (rc || !c.dbg) return rc;
     // every radix sort clears its error word (onesweep: with its control block; multi-kernel: pass 0)
     return check_lookback_flags(c.stream, c.dev, c.g.counters, c.bucket ? nullptr : c.g.sort.ctrl + RS_CTRL_ERR,
@@ -1186,6 +1238,8 @@ struct BwdCall : RasterState {
     bool feat_bwd;   // the feature work of this call: only with an upstream gradient of the feature image
     DistortionExt dx;
     bool dist_bwd;   // the distortion work of this call: only with an upstream gradient of the map
+    MedianExt mx;
+    bool med_bwd;    // the median work of this call: only with an upstream gradient of the median depth
     int64_t g0, g1;  // the Gaussians of the per-Gaussian stage
     BwdScratch sc;
     GatherSrc src;   // what every gather of this call tests (live: null with "bwd_live" 0, decided once)
@@ -1195,7 +1249,7 @@ struct BwdCall : RasterState {
 // The side structs and every argument check, in the order callers see their errors.  With P == 0 it ends after the
 // checks an empty scene needs (as check_common does).
 static int bwd_check_args(BwdCall &c, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
-                          const gsr_features_ext *feat, const gsr_distortion_ext *dist) {
+                          const gsr_features_ext *feat, const gsr_distortion_ext *dist, const gsr_median_ext *median) {
     const gsr_backward_args *a = c.a;
     int rc = read_composite_ext(ext, a->background, c.e);
     if (rc) return rc;
@@ -1214,6 +1268,13 @@ static int bwd_check_args(BwdCall &c, const gsr_composite_ext *ext, const gsr_ab
     if (c.dx.given && a->stages != GSR_BWD_ALL)
         return fail(GSR_ERR_UNSUPPORTED, "distortion with a split backward (stages != GSR_BWD_ALL) is not built");
     c.dist_bwd = c.dx.given && c.dx.dL_dD != nullptr;
+    rc = read_median_ext(median, c.mx);
+    if (rc) return rc;
+    if (c.mx.given && c.ab.dL_dmeans2D_abs)
+        return fail(GSR_ERR_UNSUPPORTED, "median depth with gsr_absgrad_ext.dL_dmeans2D_abs is not built");
+    if (c.mx.given && a->stages != GSR_BWD_ALL)
+        return fail(GSR_ERR_UNSUPPORTED, "median depth with a split backward (stages != GSR_BWD_ALL) is not built");
+    c.med_bwd = c.mx.given && c.mx.dL_dmedian != nullptr;
     if (c.ab.densify_abs && !a->densify_stats)
         return fail(GSR_ERR_ARG, "gsr_absgrad_ext.densify_abs needs densify_stats");
     if (c.ab.densify_abs && !c.ab.dL_dmeans2D_abs)
@@ -1345,6 +1406,20 @@ static int bwd_distortion(BwdCall &c) {
     return GSR_OK;
 }
 
+// The median walk adds, as inverse-depth weight, each selected instance's summed upstream gradient into the rows (and
+// marks the live flags)
+static int bwd_median(BwdCall &c) {
+    hipStream_t stream = c.stream;
+    MedianBwdParams mp;
+    mp.src = replay_src(c);
+    mp.depth_key = c.g.depth_key;
+    mp.pos = c.mx.pos; mp.dL_dmedian = c.mx.dL_dmedian;
+    mp.rows = c.sc.rows;
+    mp.live = c.src.live ? c.g.live : nullptr;
+    GSR_STAGE(ST_MEDIAN_BWD, c.dbg, launch_median_bwd(stream, mp));
+    return GSR_OK;
+}
+
 // The big Gaussians' rows (and abs rows), summed by a workgroup each
 static int bwd_big_reduce(BwdCall &c) {
     hipStream_t stream = c.stream;
@@ -1376,7 +1451,7 @@ static int bwd_gaussians(BwdCall &c) {
     pp.focal_y = a->H / (2.0f * a->tan_fovy);
     pp.scale_modifier = a->scale_modifier;
     pp.antialiasing = a->antialiasing;
-    pp.has_invdepth = a->dL_dinvdepth != nullptr || (c.dist_bwd && c.R > 0);  // (the distortion's depth term: rows[..][9])
+    pp.has_invdepth = a->dL_dinvdepth != nullptr || ((c.dist_bwd || c.med_bwd) && c.R > 0);  // (the distortion's depth term, the median's: rows[..][9])
     pp.means3D = a->means3D; pp.opacities = a->opacities; pp.scales = a->scales; pp.rotations = a->rotations;
     pp.cov3D_precomp = a->cov3D_precomp; pp.shs = (a->colors_precomp ? nullptr : a->shs);
     pp.view = a->viewmatrix; pp.proj = a->projmatrix; pp.campos = a->campos;
@@ -1446,12 +1521,18 @@ int gsr_backward_features(const gsr_backward_args *a, const gsr_composite_ext *e
 int gsr_backward_distortion(const gsr_backward_args *a, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
                             const gsr_features_ext *feat, const gsr_distortion_ext *dist, gsr_alloc_fn alloc,
                             void *alloc_ctx, void *stream_ptr) {
+    return gsr_backward_median(a, ext, absgrad, feat, dist, nullptr, alloc, alloc_ctx, stream_ptr);
+}
+
+int gsr_backward_median(const gsr_backward_args *a, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
+                        const gsr_features_ext *feat, const gsr_distortion_ext *dist, const gsr_median_ext *median,
+                        gsr_alloc_fn alloc, void *alloc_ctx, void *stream_ptr) {
     if (!a || !alloc) return fail(GSR_ERR_ARG, "null argument");
     BwdCall c{};
     c.a = a; c.alloc = alloc; c.alloc_ctx = alloc_ctx;
     c.stream = (hipStream_t)stream_ptr; c.dbg = a->debug != 0;
     hipStream_t stream = c.stream;
-    int rc = bwd_check_args(c, ext, absgrad, feat, dist);
+    int rc = bwd_check_args(c, ext, absgrad, feat, dist, median);
     if (rc) return rc;
     if (a->P == 0) {  // no Gaussian: the background's gradients with T_final = 1, the camera's empty sums
         if (!camera_grads(a) && !c.e.dL_dbackground && !c.e.dL_dbackground_image) return GSR_OK;
@@ -1468,6 +1549,7 @@ int gsr_backward_distortion(const gsr_backward_args *a, const gsr_composite_ext 
             rc = bwd_composite(c);
             if (!rc && c.feat_bwd) rc = bwd_features(c);
             if (!rc && c.dist_bwd) rc = bwd_distortion(c);
+            if (!rc && c.med_bwd) rc = bwd_median(c);
             if (!rc) rc = bwd_big_reduce(c);
             if (rc) return rc;
         }
@@ -2276,6 +2358,48 @@ int gsr_normal_consistency_backward(int H, int W, float tanfovx, float tanfovy, 
     if (!D || !A || !N || !dE || !dD || !dA || !dN) return fail(GSR_ERR_ARG, "normal consistency: null array");
     NormalArgs a = normal_args(H, W, tanfovx, tanfovy);
     a.D = D; a.A = A; a.N = N; a.dE = dE; a.dD = dD; a.dA = dA; a.dN = dN;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_normal_consistency_backward((hipStream_t)stream_ptr, a);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_normal_consistency_forward_surface(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A,
+                                           const float *N, const float *M, float depth_ratio, float *E, float *n_d,
+                                           void *stream_ptr) {
+    if (const char *e = normal_shape_error(H, W, tanfovx, tanfovy)) return fail(GSR_ERR_ARG, e);
+    if (!D || !A || !N || !M || !E) return fail(GSR_ERR_ARG, "normal consistency: null array");
+    if (!std::isfinite(depth_ratio)) return fail(GSR_ERR_ARG, "normal consistency: depth_ratio must be finite");
+    NormalArgs a = normal_args(H, W, tanfovx, tanfovy);
+    a.D = D; a.A = A; a.N = N; a.E = E; a.n_d = n_d; a.Md = M; a.ratio = depth_ratio;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_normal_consistency_forward((hipStream_t)stream_ptr, a);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_depth_to_normal_surface(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A,
+                                const float *M, float depth_ratio, float *n_d, void *stream_ptr) {
+    if (const char *e = normal_shape_error(H, W, tanfovx, tanfovy)) return fail(GSR_ERR_ARG, e);
+    if (!D || !A || !M || !n_d) return fail(GSR_ERR_ARG, "normal consistency: null array");
+    if (!std::isfinite(depth_ratio)) return fail(GSR_ERR_ARG, "normal consistency: depth_ratio must be finite");
+    NormalArgs a = normal_args(H, W, tanfovx, tanfovy);
+    a.D = D; a.A = A; a.n_d = n_d; a.Md = M; a.ratio = depth_ratio;
+    StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
+    launch_normal_consistency_forward((hipStream_t)stream_ptr, a);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_normal_consistency_backward_surface(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A,
+                                            const float *N, const float *M, float depth_ratio, const float *dE,
+                                            float *dD, float *dA, float *dN, float *dM, void *stream_ptr) {
+    if (const char *e = normal_shape_error(H, W, tanfovx, tanfovy)) return fail(GSR_ERR_ARG, e);
+    if (!D || !A || !N || !M || !dE || !dD || !dA || !dN || !dM)
+        return fail(GSR_ERR_ARG, "normal consistency: null array");
+    if (!std::isfinite(depth_ratio)) return fail(GSR_ERR_ARG, "normal consistency: depth_ratio must be finite");
+    NormalArgs a = normal_args(H, W, tanfovx, tanfovy);
+    a.D = D; a.A = A; a.N = N; a.dE = dE; a.dD = dD; a.dA = dA; a.dN = dN; a.Md = M; a.ratio = depth_ratio; a.dM = dM;
     StreamDeviceGuard device_guard((hipStream_t)stream_ptr);
     launch_normal_consistency_backward((hipStream_t)stream_ptr, a);
     GSR_HIP(hipGetLastError());

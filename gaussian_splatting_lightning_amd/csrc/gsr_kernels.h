@@ -367,6 +367,30 @@ struct DistBwdParams {
 };
 void launch_dist_bwd(hipStream_t s, const DistBwdParams &p);
 
+// ---- median depth map (gsr_median.hip) ----
+// Per pixel the pair at which the colour forward's transmittance crosses 1/2 (the last contributor whose incoming T
+// exceeds 0.5), replayed from its recorded state: the pair's position in the tile's sorted list, its Gaussian id and
+// that Gaussian's view depth (-1, -1, 0 where no Gaussian reaches); all three fully written
+struct MedianFwdParams {
+    ReplaySrc src;
+    const uint32_t *depth_key;  // P: float bits of the view depth (GeomState::depth_key)
+    float *out_depth;           // (H,W)
+    int32_t *out_index, *out_pos;
+};
+void launch_median_fwd(hipStream_t s, const MedianFwdParams &p);
+// The median backward, after launch_render_bwd (and the feature / distortion backward walks) and before
+// launch_big_reduce: per selected instance the sum of dL_dmedian over the tile's pixels that selected it, added as
+// inverse-depth weight into rows[..][9]
+struct MedianBwdParams {
+    ReplaySrc src;
+    const uint32_t *depth_key;
+    const int32_t *pos;         // (H,W): the forward's out_pos
+    const float *dL_dmedian;    // (H,W)
+    float *rows;
+    uint8_t *live;  // as RenderBwdParams::live, or null
+};
+void launch_median_bwd(hipStream_t s, const MedianBwdParams &p);
+
 // ---- per-Gaussian contribution statistics (gsr_contrib.hip) ----
 // The colour forward replayed once more, forward only: per contributing (Gaussian, pixel) pair the value
 // v = [m(pix) *] alpha_i T_i; per instance the wave's count, sum and max of v go to the instance's 16-B row
@@ -640,6 +664,10 @@ struct NormalArgs {
     float *E, *n_d;           // forward: (1,H,W), (3,H,W); either may be null
     const float *dE;          // backward: (1,H,W)
     float *dD, *dA, *dN;      // backward: (1,H,W) (1,H,W) (3,H,W)
+    // the blended surface d = (1 - r) D / A + r m (the *_surface entry points; null / 0 otherwise: d = D / A)
+    const float *Md;          // (1,H,W) the median depth m, or null
+    float ratio;              // r (2DGS's depth_ratio)
+    float *dM;                // backward: (1,H,W), with Md
 };
 void launch_normal_consistency_forward(hipStream_t s, const NormalArgs &A);
 void launch_normal_consistency_backward(hipStream_t s, const NormalArgs &A);

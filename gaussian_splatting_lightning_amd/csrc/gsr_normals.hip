@@ -146,11 +146,23 @@ __device__ __forceinline__ float3 nc_centre(const NormalArgs &A, int x, int y, f
 }
 
 __device__ __forceinline__ float nc_depth(float D, float A) { return A > 0.f ? D / A : 0.f; }
+// The surface at pixel p.  SURF (the *_surface entry points): the blend d = (1 - r) D / A + r m of the expected depth
+// and the median depth m (2DGS's depth_ratio r), 0 where A == 0; else d = D / A, the arithmetic it always had.
+template <bool SURF>
+__device__ __forceinline__ float nc_surface(const NormalArgs &A, size_t p) {
+    if constexpr (SURF) {
+        const float a = A.A[p];
+        return a > 0.f ? (1.0f - A.ratio) * (A.D[p] / a) + A.ratio * A.Md[p] : 0.f;
+    } else {
+        return nc_depth(A.D[p], A.A[p]);
+    }
+}
 
 // 1 / |c| from |c|^2 > 0: one correctly rounded square root and one division per centre, then multiplications (with a
 // division per component, 25 more per pixel, the backward took 0.059 ms at 1080p instead of 0.049).
 __device__ __forceinline__ float nc_inv_norm(float l2) { return 1.0f / sqrtf(l2); }
 
+template <bool SURF>
 __global__ __launch_bounds__(256) void normal_consistency_forward_kernel(NormalArgs A) {
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
     if (x >= A.W || y >= A.H) return;
@@ -159,8 +171,8 @@ __global__ __launch_bounds__(256) void normal_consistency_forward_kernel(NormalA
     if (nc_interior(A, x, y)) {
         const size_t up = p - A.W, dn = p + A.W;
         float3 dv, dh;
-        const float3 c = nc_centre(A, x, y, nc_depth(A.D[dn], A.A[dn]), nc_depth(A.D[up], A.A[up]),
-                                   nc_depth(A.D[p + 1], A.A[p + 1]), nc_depth(A.D[p - 1], A.A[p - 1]), dv, dh);
+        const float3 c = nc_centre(A, x, y, nc_surface<SURF>(A, dn), nc_surface<SURF>(A, up),
+                                   nc_surface<SURF>(A, p + 1), nc_surface<SURF>(A, p - 1), dv, dh);
         const float l2 = c.x * c.x + c.y * c.y + c.z * c.z;
         if (l2 > 0.f) {
             const float il = nc_inv_norm(l2);
@@ -180,7 +192,8 @@ __global__ __launch_bounds__(256) void normal_consistency_forward_kernel(NormalA
 
 void launch_normal_consistency_forward(hipStream_t s, const NormalArgs &A) {
     const dim3 grid((unsigned)((A.W + 63) / 64), (unsigned)((A.H + 3) / 4));
-    normal_consistency_forward_kernel<<<grid, dim3(64, 4), 0, s>>>(A);
+    if (A.Md) normal_consistency_forward_kernel<true><<<grid, dim3(64, 4), 0, s>>>(A);
+    else normal_consistency_forward_kernel<false><<<grid, dim3(64, 4), 0, s>>>(A);
 }
 
 // What centre (x, y) hands to the points that made its cross product: gv = dL/d(Pt(x, y+1) - Pt(x, y-1)) and
@@ -209,6 +222,7 @@ __device__ __forceinline__ NcCentreGrad nc_centre_grad(const NormalArgs &A, int 
     return r;
 }
 
+template <bool SURF>
 __global__ __launch_bounds__(256) void normal_consistency_backward_kernel(NormalArgs A) {
     __shared__ float sd[NC_DH][NC_DW];
     __shared__ float sG[3][NC_GH][NC_GW];
@@ -220,8 +234,7 @@ __global__ __launch_bounds__(256) void normal_consistency_backward_kernel(Normal
         const int x = x0 - 2 + lx, y = y0 - 2 + ly;
         float d = 0.f;
         if (x >= 0 && x < A.W && y >= 0 && y < A.H) {
-            const size_t p = (size_t)y * A.W + x;
-            d = nc_depth(A.D[p], A.A[p]);
+            d = nc_surface<SURF>(A, (size_t)y * A.W + x);
         }
         sd[ly][lx] = d;
     }
@@ -261,8 +274,15 @@ __global__ __launch_bounds__(256) void normal_consistency_backward_kernel(Normal
         const size_t p = (size_t)y * A.W + x;
         const float a = A.A[p];
         const bool live = a > 0.f;
-        A.dD[p] = live ? dd / a : 0.f;
-        A.dA[p] = live ? -dd * sd[ly + 2][lx + 2] / a : 0.f;  // d(D / A)/dA = -d / A
+        if constexpr (SURF) {  // dd splits: (1 - r) of it to the expected depth D / A, r of it to the median
+            const float de = (1.0f - A.ratio) * dd;
+            A.dD[p] = live ? de / a : 0.f;
+            A.dA[p] = live ? -de * (A.D[p] / a) / a : 0.f;
+            A.dM[p] = live ? A.ratio * dd : 0.f;
+        } else {
+            A.dD[p] = live ? dd / a : 0.f;
+            A.dA[p] = live ? -dd * sd[ly + 2][lx + 2] / a : 0.f;  // d(D / A)/dA = -d / A
+        }
         const float w = nc_interior(A, x, y) ? A.dE[p] * a : 0.f;
         A.dN[p] = -w * me.n.x;
         A.dN[HW + p] = -w * me.n.y;
@@ -272,7 +292,8 @@ __global__ __launch_bounds__(256) void normal_consistency_backward_kernel(Normal
 
 void launch_normal_consistency_backward(hipStream_t s, const NormalArgs &A) {
     const dim3 grid((unsigned)((A.W + NC_TW - 1) / NC_TW), (unsigned)((A.H + NC_TH - 1) / NC_TH));
-    normal_consistency_backward_kernel<<<grid, dim3(64, 4), 0, s>>>(A);
+    if (A.Md) normal_consistency_backward_kernel<true><<<grid, dim3(64, 4), 0, s>>>(A);
+    else normal_consistency_backward_kernel<false><<<grid, dim3(64, 4), 0, s>>>(A);
 }
 
 }  // namespace gsr

@@ -23,6 +23,10 @@ GaussianRasterizer(settings, distortion="z" | "ndc") / rasterize_gaussians(..., 
 distortion map (1,H,W) = sum_i sum_j w_i w_j |t_i - t_j| of Mip-NeRF 360 (2DGS's distloss) as the last output, after
 the feature image: t the view depth ("z") or 2DGS's far / (far - near) (1 - near / z) ("ndc", distortion_near /
 distortion_far), differentiable through the weights and through t (gsr_forward_distortion / gsr_backward_distortion).
+GaussianRasterizer(settings, median_depth=True) / rasterize_gaussians(..., median_depth=True) also return, as the last two
+outputs, median_depth (1,H,W) float32 and median_index (1,H,W) int32: the view depth and the id of the Gaussian at which
+the pixel's transmittance crosses 1/2 (2DGS's depth_ratio = 1 surface; 0 and -1 where no Gaussian reaches).  The depth
+is differentiable with respect to the selected Gaussian's depth alone (gsr_forward_median / gsr_backward_median).
 Every computation runs in the HIP kernels on the tensors' device; the scratch state the backward needs
 (geometry/binning/image buffers) lives in uint8 tensors saved on the autograd context.
 """
@@ -144,10 +148,21 @@ class DistortionState(NamedTuple):
     totals: torch.Tensor
 
 
-class _DistortionForwardState(ForwardState):
-    """A ForwardState that also carries a DistortionState as .distortion -- an attribute, not a field: the fields of
-    ForwardState, their count and their order are what earlier callers construct and index."""
+class MedianState(NamedTuple):
+    """What a forward with a median depth map leaves for its backward: per pixel the selected pair's position in its
+    tile's sorted list, (H,W) int32, -1 where no Gaussian reaches."""
+    pos: torch.Tensor
+
+
+class _ExtendedForwardState(ForwardState):
+    """A ForwardState that also carries a DistortionState as .distortion and / or a MedianState as .median --
+    attributes, not fields: the fields of ForwardState, their count and their order are what earlier callers construct
+    and index."""
     distortion: Optional[DistortionState] = None
+    median: Optional[MedianState] = None
+
+
+_DistortionForwardState = _ExtendedForwardState  # its name while the distortion map was the only such attribute
 
 
 def _distortion(distortion, near, far):
@@ -191,7 +206,8 @@ def _features(features, P: int, device):
 
 
 def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                return_alpha=False, features=None, distortion=None, distortion_near=None, distortion_far=None):
+                return_alpha=False, features=None, distortion=None, distortion_near=None, distortion_far=None,
+                median_depth=False):
     """One call of gsr_forward.  Returns (color (3,H,W), radii (P,), invdepth (1,H,W), ForwardState).
     raster_settings.bg is the (3,) background or a (3,H,W) image, one background per pixel.  return_alpha=True returns
     (color, radii, invdepth, alpha (1,H,W), ForwardState), alpha = 1 - the transmittance left behind the pixel's last
@@ -205,7 +221,11 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
     contributors, with the colour's weights and no background term (exactly 0 where no Gaussian reaches), is returned
     last before the state, after the feature image; t is the view depth ("z") or far / (far - near) (1 - near / z)
     ("ndc": distortion_near, distortion_far, 0 < near < far).  The state then carries .distortion, a DistortionState
-    (gsr_forward_distortion); every other output keeps its bits."""
+    (gsr_forward_distortion); every other output keeps its bits.
+    median_depth=True: median_depth (1,H,W) float32 and median_index (1,H,W) int32 are returned last before the state,
+    after the distortion map: the view depth and the id of the last contributor the pixel's transmittance reaches above
+    1/2 (the last contributor at all on a pixel that never becomes half opaque; 0 and -1 where no Gaussian reaches).
+    The state then carries .median, a MedianState (gsr_forward_median); every other output keeps its bits."""
     dist_spec = _distortion(distortion, distortion_near, distortion_far)
     lib = _native.load()
     device = means3D.device
@@ -250,6 +270,13 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
         dist = _native.DistortionExt(map=_native.DISTORTION_MAPS[dist_spec[0]], near_plane=dist_spec[1],
                                      far_plane=dist_spec[2], out_distortion=dist_image.data_ptr(),
                                      total_weight=totals[0].data_ptr(), total_moment=totals[1].data_ptr())
+    med_depth = med_index = med_pos = med = None
+    if median_depth:
+        med_depth = torch.empty(1, H, W, dtype=torch.float32, device=device)
+        med_index = torch.empty(1, H, W, dtype=torch.int32, device=device)
+        med_pos = torch.empty(H, W, dtype=torch.int32, device=device)
+        med = _native.MedianExt(out_median_depth=med_depth.data_ptr(), out_median_index=med_index.data_ptr(),
+                                median_pos=med_pos.data_ptr())
     bufs = _Buffers(device)
     a = _native.ForwardArgs(
         P=P, D=int(rs.sh_degree), M=M, W=W, H=H, background=None if bg_image else _ptr(bg), means3D=_ptr(means3D_c),
@@ -261,17 +288,22 @@ def forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D
         out_invdepth=invdepth.data_ptr(), radii=radii.data_ptr())
     num_rendered = ctypes.c_int64(0)
     with torch.cuda.device(device):  # the library also switches to its stream's device (gsr_api.hip)
-        rc = _native.call_forward(lib, a, ext, feat, bufs.callback, _stream_handle(device), num_rendered, dist=dist)
+        rc = _native.call_forward(lib, a, ext, feat, bufs.callback, _stream_handle(device), num_rendered, dist=dist,
+                                  median=med)
     bufs.raise_pending()
     _native.check(rc, "rasterize_gaussians")
     state = ForwardState(means3D_c, sh_c, col_c, op_c, sc_c, rot_c, cov_c, radii, bg, view, proj, campos,
                          bufs.get(_native.GSR_BUF_GEOM), bufs.get(_native.GSR_BUF_BINNING),
                          bufs.get(_native.GSR_BUF_IMAGE), int(num_rendered.value), int(a.num_big_out), M, feat_c)
     res = (color, radii, invdepth) + ((alpha,) if return_alpha else ()) + ((feat_image,) if feat is not None else ())
+    if dist is not None or med is not None:
+        state = _ExtendedForwardState(*state)
     if dist is not None:
-        state = _DistortionForwardState(*state)
         state.distortion = DistortionState(*dist_spec, totals)
         res += (dist_image,)
+    if med is not None:
+        state.median = MedianState(med_pos)
+        res += (med_depth, med_index)
     return (*res, state)
 
 
@@ -282,15 +314,16 @@ class _Upstream(NamedTuple):
     alpha: Optional[torch.Tensor]
     features: Optional[torch.Tensor]
     distortion: Optional[torch.Tensor]
+    median: Optional[torch.Tensor]
     bg_image: bool                         # the forward's background is a (3,H,W) image
     ext: Optional[_native.CompositeExt]    # the backward's gsr_composite_ext, None for the plain call
 
 
 def _upstream(st: ForwardState, rs, grad_color, grad_depth, grad_alpha=None, grad_features=None, dbg=None,
-              grad_distortion=None):
+              grad_distortion=None, grad_median=None):
     """The upstream gradients of colour (zeros when None), inverse depth, alpha ((1,H,W) or (H,W)) and the feature image
-    ((C,H,W), only for a state with features) and the distortion map ((1,H,W) or (H,W), only for a state with
-    distortion), checked and made contiguous float32, and the call's CompositeExt: given
+    ((C,H,W), only for a state with features), the distortion map ((1,H,W) or (H,W), only for a state with
+    distortion) and the median depth ((1,H,W) or (H,W), only for a state with the median), checked and made contiguous float32, and the call's CompositeExt: given
     with a background image, an alpha gradient or dbg, the destination of the background's gradient."""
     H, W = int(rs.image_height), int(rs.image_width)
     if grad_color is None:
@@ -315,13 +348,19 @@ def _upstream(st: ForwardState, rs, grad_color, grad_depth, grad_alpha=None, gra
         if grad_distortion.numel() != H * W or grad_distortion.ndim not in (2, 3):
             raise RuntimeError(f"grad_out_distortion must have shape (1, {H}, {W}), got {tuple(grad_distortion.shape)}")
         grad_distortion = grad_distortion.to(torch.float32).contiguous()
+    if grad_median is not None:
+        if getattr(st, "median", None) is None:
+            raise RuntimeError("grad_out_median_depth needs a state from forward_raw(..., median_depth=True)")
+        if grad_median.numel() != H * W or grad_median.ndim not in (2, 3):
+            raise RuntimeError(f"grad_out_median_depth must have shape (1, {H}, {W}), got {tuple(grad_median.shape)}")
+        grad_median = grad_median.to(torch.float32).contiguous()
     bg_image = _background(st.bg, H, W)
     ext = None
     if bg_image or grad_alpha is not None or dbg is not None:
         ext = _native.CompositeExt(background_image=_ptr(st.bg) if bg_image else None, dL_dalpha=_ptr(grad_alpha),
                                    dL_dbackground=None if bg_image else _ptr(dbg),
                                    dL_dbackground_image=_ptr(dbg) if bg_image else None)
-    return _Upstream(grad_color, grad_depth, grad_alpha, grad_features, grad_distortion, bg_image, ext)
+    return _Upstream(grad_color, grad_depth, grad_alpha, grad_features, grad_distortion, grad_median, bg_image, ext)
 
 
 def _backward_args(st: ForwardState, rs, up: _Upstream, accumulate_stats, **fields):
@@ -349,7 +388,7 @@ def _absgrad_ext(dabs: torch.Tensor, abs_stats, n: int):
 def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_depth=None, out=None,
                  compact_sh=False, accumulate_stats=False, camera_grads=False, grad_out_alpha=None,
                  background_grad=False, absgrad=False, abs_stats=False, grad_out_features=None,
-                 grad_out_distortion=None):
+                 grad_out_distortion=None, grad_out_median_depth=None):
     """One call of gsr_backward.  Returns a dict of gradients (means3D, means2D, shs, colors_precomp,
     opacities, scales, rotations, cov3D_precomp); entries are None where the input was absent.
     `out` may supply preallocated contiguous float32 destinations (e.g. views into one flat buffer that is
@@ -386,7 +425,13 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     the upstream gradient of the distortion map: through the weights and through the Gaussians' depths it enters every
     other gradient of the call, the camera's included, in a fixed summation order.  With grad_out_distortion=None
     every gradient has the bits of the call without distortion.  The call is then gsr_backward_distortion; absgrad /
-    abs_stats with it raise NotImplementedError."""
+    abs_stats with it raise NotImplementedError.
+    grad_out_median_depth (1,H,W) or (H,W), for a state that carries the median (forward_raw(..., median_depth=True)),
+    is the upstream gradient of median_depth.  The selection is piecewise constant: the gradient reaches only the depth
+    of each pixel's selected Gaussian, and through it means3D and the camera, in a fixed summation order; opacities,
+    scales, rotations, means2D and the colours get nothing from it.  With grad_out_median_depth=None every gradient
+    has the bits of the call without the median.  The call is then gsr_backward_median; absgrad / abs_stats with it
+    raise NotImplementedError."""
     if abs_stats and "densify_stats" not in (out or {}):
         raise RuntimeError("abs_stats=True needs out['densify_stats']")
     lib = _native.load()
@@ -427,7 +472,7 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
     dcampos = dst("campos", 3) if camera_grads else None
     dbg = dst("bg", *st.bg.shape) if (background_grad or "bg" in out) else None
     up = _upstream(st, rs, grad_out_color, grad_out_depth, grad_out_alpha, grad_out_features, dbg,
-                   grad_out_distortion)
+                   grad_out_distortion, grad_out_median_depth)
     feat = dfeat = None
     if st.features is not None:
         C = int(st.features.shape[1])
@@ -440,7 +485,12 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
         dist = _native.DistortionExt(map=_native.DISTORTION_MAPS[ds.map], near_plane=ds.near, far_plane=ds.far,
                                      total_weight=ds.totals[0].data_ptr(), total_moment=ds.totals[1].data_ptr(),
                                      dL_ddistortion=_ptr(up.distortion))
-    # (features or distortion with absgrad: refused by the library, GSR_ERR_UNSUPPORTED -> NotImplementedError)
+    med = None
+    ms = getattr(st, "median", None)
+    if ms is not None:
+        med = _native.MedianExt(median_pos=ms.pos.data_ptr(), dL_dmedian_depth=_ptr(up.median))
+    # (features, distortion or the median with absgrad: refused by the library, GSR_ERR_UNSUPPORTED ->
+    # NotImplementedError)
     ab = None if dabs is None else _absgrad_ext(dabs, abs_stats, P)
     bufs = _Buffers(device)
     a = _backward_args(
@@ -453,7 +503,7 @@ def backward_raw(state: ForwardState, raster_settings, grad_out_color, grad_out_
         dL_dviewmatrix=_ptr(dview), dL_dprojmatrix=_ptr(dproj), dL_dcampos=_ptr(dcampos))
     with torch.cuda.device(device):
         rc = _native.call_backward(lib, a, ext=up.ext, absgrad=ab, feat=feat, cb=bufs.callback,
-                                   stream=_stream_handle(device), dist=dist)
+                                   stream=_stream_handle(device), dist=dist, median=med)
     bufs.raise_pending()
     _native.check(rc, "rasterize_gaussians_backward")
     camera = dict(viewmatrix=dview, projmatrix=dproj, campos=dcampos) if camera_grads else {}
@@ -562,13 +612,16 @@ def backward_chunked(state: ForwardState, raster_settings, grad_out_color, grad_
     every chunk must, since the compositing call produces the rows they are summed from.  abs_stats=True forms each
     chunk's densify_stats[:, 0] from it (every chunk then needs both).
     A state that carries features raises NotImplementedError: the split backward of feature channels is not built;
-    so does a state that carries distortion."""
+    so does a state that carries distortion or the median depth."""
     lib = _native.load()
     rs = raster_settings
     st = state
     if getattr(st, "distortion", None) is not None:
         raise NotImplementedError("backward_chunked: a forward state with distortion needs backward_raw (the split "
                                   "backward of the distortion map is not built)")
+    if getattr(st, "median", None) is not None:
+        raise NotImplementedError("backward_chunked: a forward state with the median depth needs backward_raw (the "
+                                  "split backward of the median depth is not built)")
     if st.features is not None:
         raise NotImplementedError("backward_chunked: a forward state with features needs backward_raw (the split "
                                   "backward of feature channels is not built)")
@@ -658,7 +711,10 @@ def _campos_rows(spec):
 def _save_state(ctx, st: ForwardState):
     """Keep a ForwardState on an autograd context: its tensors saved (an empty one in place of None), the rest plain."""
     ds = getattr(st, "distortion", None)
-    tensors = st[:15] + (() if st.features is None else (st.features,)) + (() if ds is None else (ds.totals,))
+    ms = getattr(st, "median", None)
+    tensors = (st[:15] + (() if st.features is None else (st.features,)) + (() if ds is None else (ds.totals,))
+               + (() if ms is None else (ms.pos,)))
+    ctx.has_median = ms is not None
     ctx.meta = (st.num_rendered, st.num_big, st.M)
     ctx.has_features = st.features is not None
     ctx.distortion = None if ds is None else tuple(ds[:3])
@@ -671,10 +727,13 @@ def _saved_state(ctx) -> ForwardState:
     tensors = [t if present else None for t, present in zip(ctx.saved_tensors, ctx.present)]
     extra = tensors[15:]
     features = extra.pop(0) if ctx.has_features else None
-    if ctx.distortion is None:
+    if ctx.distortion is None and not ctx.has_median:
         return ForwardState(*tensors[:15], *ctx.meta, features)
-    st = _DistortionForwardState(*tensors[:15], *ctx.meta, features)
-    st.distortion = DistortionState(*ctx.distortion, extra.pop(0))
+    st = _ExtendedForwardState(*tensors[:15], *ctx.meta, features)
+    if ctx.distortion is not None:
+        st.distortion = DistortionState(*ctx.distortion, extra.pop(0))
+    if ctx.has_median:
+        st.median = MedianState(extra.pop(0))
     return st
 
 
@@ -682,14 +741,15 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, flags=(False, False), features=None, bg=None, *camera):
-        # flags: (return_alpha, absgrad[, distortion: None or (map, near, far)]).  features: None or the (P,C) channels.  bg: None or the settings' bg once
+        # flags: (return_alpha, absgrad[, distortion: None or (map, near, far)[, median_depth]]).  features: None or the (P,C) channels.  bg: None or the settings' bg once
         # more, camera: () or the settings' (viewmatrix, projmatrix, campos) once more, as inputs autograd can hand a
         # gradient to (rasterize_gaussians); the values are read from the settings either way
         return_alpha, absgrad = flags[:2]
         dmap, dnear, dfar = (flags[2] if len(flags) > 2 and flags[2] is not None else (None, None, None))
+        median_depth = len(flags) > 3 and bool(flags[3])
         res = forward_raw(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                           return_alpha=return_alpha, features=features, distortion=dmap, distortion_near=dnear,
-                          distortion_far=dfar)
+                          distortion_far=dfar, median_depth=median_depth)
         ctx.raster_settings = raster_settings
         ctx.return_alpha = bool(return_alpha)
         # absgrad: the backward sets means2D.absgrad on the caller's tensor (as gsplat's does)
@@ -698,7 +758,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.camera = [(tuple(t.shape), t.device) for t in camera]
         _save_state(ctx, res[-1])
         ctx.set_materialize_grads(False)
-        return res[:-1]  # (color, radii, invdepth[, alpha][, feature_image][, distortion])
+        if median_depth:
+            ctx.mark_non_differentiable(res[-2])  # median_index
+        return res[:-1]  # (color, radii, invdepth[, alpha][, feature_image][, distortion][, median_depth, median_index])
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, *rest):
@@ -707,10 +769,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         grad_out_alpha = rest.pop(0) if ctx.return_alpha else None
         grad_out_features = rest.pop(0) if st.features is not None else None
         grad_out_distortion = rest.pop(0) if getattr(st, "distortion", None) is not None else None
+        grad_out_median = rest.pop(0) if getattr(st, "median", None) is not None else None  # (then the index's: None)
         need = ctx.needs_input_grad
         g = backward_raw(st, ctx.raster_settings, grad_out_color, grad_out_depth, camera_grads=any(need[12:]),
                          grad_out_alpha=grad_out_alpha, background_grad=need[11], absgrad=ctx.absgrad_of is not None,
-                         grad_out_features=grad_out_features, grad_out_distortion=grad_out_distortion)
+                         grad_out_features=grad_out_features, grad_out_distortion=grad_out_distortion,
+                         grad_out_median_depth=grad_out_median)
         if ctx.absgrad_of is not None:  # (P,3) with z = 0, so code that takes [:, :2] of means2D.grad works on it
             m2a = g["means2D_abs"]
             ctx.absgrad_of.absgrad = torch.cat([m2a, m2a.new_zeros(m2a.shape[0], 1)], dim=1)
@@ -732,7 +796,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, return_alpha=False, absgrad=False, features=None, distortion=None,
-                        distortion_near=None, distortion_far=None):
+                        distortion_near=None, distortion_far=None, median_depth=False):
     """Differentiable with respect to the Gaussians' tensors and, where raster_settings.viewmatrix, .projmatrix or
     .campos requires grad, to those three as independent inputs (projmatrix being the full view-projection product:
     a caller optimising a pose builds projmatrix and campos from its view matrix in torch, which chains the three).
@@ -750,12 +814,18 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     alpha.  With absgrad=True it raises NotImplementedError (the absolute sums of a joint call are not built).
     distortion "z" or "ndc" (with distortion_near, distortion_far): the call's last output is the depth distortion map
     (1,H,W) = sum_i sum_j w_i w_j |t_i - t_j| (forward_raw).  It takes part in autograd: a loss on it reaches means3D,
-    opacities, scales, rotations, means2D.grad and the camera.  With absgrad=True it raises NotImplementedError."""
+    opacities, scales, rotations, means2D.grad and the camera.  With absgrad=True it raises NotImplementedError.
+    median_depth=True: the call's last two outputs are median_depth (1,H,W) and median_index (1,H,W) int32
+    (forward_raw).  median_depth takes part in autograd: a loss on it reaches means3D and the camera through the
+    selected Gaussians' depths, and nothing else; median_index is not differentiable.  With absgrad=True it raises
+    NotImplementedError."""
     if features is not None and absgrad:
         raise NotImplementedError("features with absgrad=True are not built yet")
     dist_spec = _distortion(distortion, distortion_near, distortion_far)
     if dist_spec is not None and absgrad:
         raise NotImplementedError("distortion with absgrad=True is not built")
+    if median_depth and absgrad:
+        raise NotImplementedError("median_depth with absgrad=True is not built")
     rs = raster_settings
     camera = (rs.viewmatrix, rs.projmatrix, rs.campos)
     if not (torch.is_grad_enabled() and all(torch.is_tensor(t) for t in camera)
@@ -764,7 +834,8 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     bg = rs.bg if (torch.is_grad_enabled() and torch.is_tensor(rs.bg) and rs.bg.requires_grad) else None
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings,
-                                     (bool(return_alpha), bool(absgrad)) + (() if dist_spec is None else (dist_spec,)),
+                                     (bool(return_alpha), bool(absgrad)) + ((dist_spec, True) if median_depth else
+                                                                            () if dist_spec is None else (dist_spec,)),
                                      features, bg, *camera)
 
 
@@ -832,12 +903,14 @@ def mark_visible(positions: torch.Tensor, viewmatrix: torch.Tensor, projmatrix: 
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings, return_alpha: bool = False,
                  absgrad: bool = False, distortion: Optional[str] = None, distortion_near: Optional[float] = None,
-                 distortion_far: Optional[float] = None):
+                 distortion_far: Optional[float] = None, median_depth: bool = False):
         """return_alpha=True: the call returns (color, radii, invdepth, alpha (1,H,W)); with P == 0 its color is the
         background where the plain call's is zero (rasterize_gaussians).  absgrad=True: the backward sets
         means2D.absgrad (rasterize_gaussians).  distortion="z" or "ndc" (with distortion_near, distortion_far): the
-        call's last output is the depth distortion map (1,H,W) (rasterize_gaussians)."""
+        call's last output is the depth distortion map (1,H,W) (rasterize_gaussians).  median_depth=True: the call's
+        last two outputs are median_depth (1,H,W) and median_index (1,H,W) int32 (rasterize_gaussians)."""
         super().__init__()
+        self.median_depth = bool(median_depth)
         self.distortion = _distortion(distortion, distortion_near, distortion_far)
         self.raster_settings = raster_settings
         self.return_alpha = bool(return_alpha)
@@ -856,11 +929,13 @@ class GaussianRasterizer(nn.Module):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or (
                 (scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-        # (color, radii, invdepth[, alpha][, feature_image (C,H,W)][, distortion (1,H,W)]): rasterize_gaussians
+        # (color, radii, invdepth[, alpha][, feature_image (C,H,W)][, distortion (1,H,W)][, median_depth (1,H,W),
+        # median_index (1,H,W)]): rasterize_gaussians
         dmap, dnear, dfar = self.distortion or (None, None, None)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs, return_alpha=self.return_alpha, absgrad=self.absgrad,
-                                   features=features, distortion=dmap, distortion_near=dnear, distortion_far=dfar)
+                                   features=features, distortion=dmap, distortion_near=dnear, distortion_far=dfar,
+                                   median_depth=self.median_depth)
 
     def contributions(self, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                       cov3D_precomp=None, pixel_weights=None, out=None, accumulate=False):

@@ -313,6 +313,49 @@ int gsr_backward_distortion(const gsr_backward_args *args, const gsr_composite_e
                             const gsr_absgrad_ext *absgrad, const gsr_features_ext *feat,
                             const gsr_distortion_ext *dist, gsr_alloc_fn alloc, void *alloc_ctx, void *stream);
 
+/* Median depth map: per pixel the view depth and the id of the Gaussian at which the ray's transmittance crosses 1/2
+ * (2DGS's depth_ratio = 1 surface, the depth its TSDF mesh extraction fuses), a fifth side struct versioned by its own
+ * size, so every other struct and GSR_ABI_VERSION stay as they are.  Over the pairs the colour forward composited, front
+ * to back (sorted index below the pixel's contributor count, the composite's alpha decision; under the "guard" knob the
+ * guarded one), with T carried from 1 as T <- T (1 - alpha): pair i is selected while the T reaching it exceeds 0.5, so
+ * the median is the last contributor whose incoming transmittance exceeds 1/2, and the last contributor at all on a
+ * pixel that never becomes half opaque.  A selection along the walk, not a weighted sum: no feature channel renders it.
+ *   forward: out_median_depth (H,W) the selected Gaussian's view depth (the float the preprocess computed, copied),
+ *     out_median_index (H,W) its id, median_pos (H,W) its position in the tile's sorted list; 0, -1 and -1 where no
+ *     Gaussian reaches; all three fully written.  median_pos is state: the backward needs it as the forward left it,
+ *     and it must be the plane the forward that built the call's geom / binning / image buffers wrote.  The library
+ *     cannot tell a stale plane, or one of another forward on the same image size, from the right one: a position at
+ *     or past the end of its tile's list is ignored (the walk stays in bounds), every other one is believed, and the
+ *     gradients are then wrong without an error.
+ *     Every other output of the call keeps the bits it has without the struct.
+ *   backward: the selection is piecewise constant, so dL_dmedian_depth (H,W) reaches only the depth of the selected
+ *     Gaussian, dL/dz_i = sum over the pixels whose median is i, and through z dL_dmeans3D and the camera gradients;
+ *     opacities, scales, rotations, means2D and colours get nothing from it.  Summed per tile in a fixed order (no float
+ *     atomics: two calls give the same bits) into the per-instance gradient rows before the per-Gaussian stage; it needs
+ *     no scratch beyond gsr_bwd_scratch_bytes (or gsr_bwd_scratch_bytes_features with features).
+ *   dL_dmedian_depth == NULL: none of the median backward is launched and every output keeps the bits it has without
+ *     the struct.
+ * With P = 0 or nothing rendered the planes are 0, -1, -1.  Together with gsr_features_ext and gsr_distortion_ext in one
+ * call: supported.
+ * GSR_ERR_ARG, before any device work or allocation: a missing out_median_depth / out_median_index (forward) or
+ * median_pos pointer; struct_size ending before the first pointer field.
+ * GSR_ERR_UNSUPPORTED, before any device work -- not built: the median together with gsr_absgrad_ext.dL_dmeans2D_abs,
+ * and with stages != GSR_BWD_ALL (the split backward). */
+typedef struct gsr_median_ext {
+    size_t struct_size;               /* sizeof as the caller was built; fields past it are read as NULL */
+    float *out_median_depth;          /* forward: (H,W), fully written */
+    int32_t *out_median_index;        /* forward: (H,W), fully written */
+    int32_t *median_pos;              /* (H,W): written by the forward, read by the backward */
+    const float *dL_dmedian_depth;    /* backward: (H,W) or NULL */
+} gsr_median_ext;
+/* gsr_forward_distortion / gsr_backward_distortion are these with median = NULL. */
+int gsr_forward_median(gsr_forward_args *args, const gsr_composite_ext *ext, const gsr_features_ext *feat,
+                       const gsr_distortion_ext *dist, const gsr_median_ext *median, gsr_alloc_fn alloc,
+                       void *alloc_ctx, void *stream, int64_t *num_rendered);
+int gsr_backward_median(const gsr_backward_args *args, const gsr_composite_ext *ext, const gsr_absgrad_ext *absgrad,
+                        const gsr_features_ext *feat, const gsr_distortion_ext *dist, const gsr_median_ext *median,
+                        gsr_alloc_fn alloc, void *alloc_ctx, void *stream);
+
 /* Per-Gaussian contribution statistics of one forward, for pruning and budgeting (LightGaussian's significance: the
  * sum; RadSplat: the max; Mini-Splatting / Taming-3DGS: the hit count; error-based densification: the sum under a
  * per-pixel error image).  Forward only: no gradient is involved.  GSR_ABI_VERSION and every other struct stay as they
@@ -628,6 +671,19 @@ int gsr_depth_to_normal(int H, int W, float tanfovx, float tanfovy, const float 
                         void *stream);
 int gsr_normal_consistency_backward(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A,
                                     const float *N, const float *dE, float *dD, float *dA, float *dN, void *stream);
+/* The same three on the blended surface d = (1 - depth_ratio) D / A + depth_ratio M where A > 0, else 0: M (1,H,W) the
+ * median depth map (gsr_median_ext.out_median_depth), depth_ratio 2DGS's (1: the median surface of its bounded scenes,
+ * 0: the expected depth), finite (GSR_ERR_ARG otherwise, and on a NULL M).  The backward hands (1 - depth_ratio) of the
+ * surface's gradient to D and A through D / A and depth_ratio of it to dM (1,H,W), written whole (0 where A == 0).  Still
+ * one launch each way, a gather, no atomics.  The functions above are unchanged: they never read a median. */
+int gsr_normal_consistency_forward_surface(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A,
+                                           const float *N, const float *M, float depth_ratio, float *E, float *n_d,
+                                           void *stream);
+int gsr_depth_to_normal_surface(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A,
+                                const float *M, float depth_ratio, float *n_d, void *stream);
+int gsr_normal_consistency_backward_surface(int H, int W, float tanfovx, float tanfovy, const float *D, const float *A,
+                                            const float *N, const float *M, float depth_ratio, const float *dE,
+                                            float *dD, float *dA, float *dN, float *dM, void *stream);
 
 /* PLY vertex records <-> parameter fields (the 3DGS checkpoint of gaussian_model.py:112-171 and
  * third_party/.../gaussian_model.py:239-314).  `records` are n fixed-size records of record_bytes each, on the
